@@ -16,22 +16,29 @@ signals, 10,000 sources; sid ~ U{0..9999}, prob ~ U[0,1) (10% of markets on the
 seed 2 + rank.  A "step" = one full pass of the hot path over the batch with inputs
 already resident in HBM: validation + consensus + per-unique outputs (sourceWeights).
 
+A plain run (no --full) sets up, warms up, times the K steps, writes its outputs when
+--dump-outputs DIR is given and prints the line; the roofline figure comes from the timed
+steps' own HIP events and costs no run of its own.  --dump-outputs writes what the last
+timed step left in the result buffers, as DIR/<name>.npy (float32 / float64): the five
+per-market outputs in full and the three per-unique outputs (sourceWeights) for a fixed,
+seeded sample of markets, slots at or past a market's n_unique zeroed.
+
 Also measured here:
   roofline      algorithmic bytes per launch / the kernel's average
                 launch time from HIP events on the launch stream, vs 8.0 TB/s; traffic =
                 the HBM bytes per launch from rocprofv3 FETCH_SIZE/WRITE_SIZE passes
                 (measurements/pmc_c2.json, written by tools/gpu_profile_c2.sh).
-  cpu_baseline  the C restatement of the reference (oracle/, kind "port"), on all the host
-                cores this process may use, over the same workload, rank 0 at N=1 only;
-                its outputs are also the full-size parity check (all eight outputs).
+  cpu_baseline  (--full) the C restatement of the reference (oracle/, kind "port"), on all
+                the host cores this process may use, over the same workload, rank 0 at N=1
+                only; its outputs are also the full-size parity check (all eight outputs).
 Before the W warmup steps the device runs the step for --prewarm-s seconds so the clocks
 have ramped (a 20-step run then matches a 200-step one); that time is reported.
 Other configs (--config c3|c4|c5|ns|agg|tb) are secondary bench lines; the default is c2,
-and at N=1 the default run also appends c3 (pre-planned), c3_fresh (planned on the GPU in the
+and at N=1 the --full run also appends c3 (pre-planned), c3_fresh (planned on the GPU in the
 step), c3_shard8 (the 8-rank split's shards timed one by one: predicted strong scaling), c3 over
 a 10M-source table, c4, tb, tb_ragged, ns (f3), agg (f4) and c5 (reduced steps, each with its
 roofline, CPU baseline where a restatement exists and full-size parity) under "secondary"
-(--no-secondary skips them).
+(--full --no-secondary skips them).
 """
 from __future__ import annotations
 
@@ -83,6 +90,13 @@ def parse(argv=None):
     p.add_argument("--events", default="region", choices=["step", "region"],
                    help="one HIP event pair around the timed region (default: per-step average "
                         "incl. the launch boundaries), or a pair around every step (~6 us per step)")
+    p.add_argument("--full", action="store_true",
+                   help="c2: also run what the headline figure does not need -- the CPU baseline, the "
+                        "full-size parity check against it (per-rank parity at N > 1) and, at N=1, the "
+                        "secondary lines; off by default")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="c2: after the timed steps write the last step's outputs as DIR/<name>.npy "
+                        "(rank 0's batch; per-unique outputs for a fixed seeded sample of markets)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=2.0, help="wall-clock budget of the CPU baseline")
     p.add_argument("--no-parity", action="store_true")
@@ -105,7 +119,7 @@ def parse(argv=None):
     p.add_argument("--graph", action="store_true",
                    help="c3: replay each step as a captured HIP graph (one launch per step)")
     p.add_argument("--no-secondary", action="store_true",
-                   help="c2 at N=1 only: skip the secondary lines (c3, c4, c5, tb) the default run appends "
+                   help="c2 at N=1 with --full only: skip the secondary lines (c3, c4, c5, tb) that run appends "
                         "under 'secondary' (each a reduced-step run of its own --config line)")
     p.add_argument("--stub", action="store_true",
                    help="launcher self-test: a CPU no-op step under gloo (no GPU, no library)")
@@ -352,6 +366,52 @@ def read_pmc(name, **match):
     return j.get("hbm_bytes_per_launch"), j.get("kernel")
 
 
+# --dump-outputs budget (64 MB in all): per-market outputs of at most this many markets (36 B
+# each, 44 with the sample's market list), per-unique outputs of a market sample of at most DUMP_UNIQUE_BYTES over three arrays
+DUMP_MARKETS = 1_100_000
+DUMP_SAMPLE_MARKETS = 16384
+DUMP_UNIQUE_BYTES = 12 << 20
+
+
+def _dump_sample(M, n, seed):
+    """All M markets, or a sorted, seeded sample of n of them."""
+    if M <= n:
+        return np.arange(M, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(M, size=n, replace=False)).astype(np.int64)
+
+
+def dump_outputs_c2(res, M, offsets, unique, path):
+    """The result buffers after the last timed step as <path>/<name>.npy (float64; n_unique
+    as float32).  Per-market outputs for every market (a seeded sample past DUMP_MARKETS,
+    listed in markets.npy); per-unique outputs for a seeded sample of markets
+    (sample_markets.npy), one row per market, the slots at or past its n_unique (which the
+    kernels never write) zeroed."""
+    os.makedirs(path, exist_ok=True)
+    save = lambda k, a, t=np.float64: np.save(os.path.join(path, k + ".npy"), a.astype(t))  # noqa: E731
+    pm = _dump_sample(M, DUMP_MARKETS, 12345)
+    sel = torch.from_numpy(pm).to(res.n_unique.device)
+    whole = len(pm) == M
+    take = lambda t: (t[:M] if whole else t[sel]).cpu().numpy()  # noqa: E731
+    if not whole:
+        save("markets", pm)
+    for k in ("consensus", "confidence", "total_weight", "err_idx"):
+        save(k, take(getattr(res, k)))
+    save("n_unique", take(res.n_unique), np.float32)
+    if not unique or M == 0:
+        return
+    W = int((offsets[1:] - offsets[:-1]).max())
+    mk = _dump_sample(M, max(1, min(DUMP_SAMPLE_MARKETS, DUMP_UNIQUE_BYTES // (24 * max(W, 1)))), 12346)
+    nu = res.n_unique[torch.from_numpy(mk).to(sel.device)].cpu().numpy().astype(np.int64)
+    col = np.arange(W, dtype=np.int64)[None, :]
+    valid = col < nu[:, None]
+    pos = np.where(valid, offsets[mk][:, None] + col, offsets[mk][:, None])
+    idx = torch.from_numpy(pos.reshape(-1)).to(sel.device)
+    save("sample_markets", mk)
+    for k in ("usid", "weight", "nweight"):
+        a = getattr(res, k)[idx].cpu().numpy().astype(np.float64).reshape(len(mk), W)
+        save(k, np.where(valid, a, 0.0))
+
+
 def bench_c2(args, world, rank):
     from bayesian_engine import _native as N, batch
 
@@ -373,6 +433,8 @@ def bench_c2(args, world, rank):
 
     wall, avg_kernel_s, prewarm = timed_loop(step, args, world, stream)
     N.check_faults(dev, "c2 timed steps")  # a kernel that gave up would leave stale outputs
+    if args.dump_outputs and rank == 0:
+        dump_outputs_c2(res, M, offsets, uniq, args.dump_outputs)
 
     # algorithmic bytes per launch
     sum_u = int(res.n_unique.sum().item())
@@ -418,13 +480,13 @@ def bench_c2(args, world, rank):
                      "bytes_per_launch": bytes_per_launch, "avg_launch_ms": avg_kernel_s * 1e3},
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cb, cpu_out = cpu_baseline_c2(offsets, sid, prob, rel, conf, present, args.cpu_seconds)
         out["cpu_baseline"] = cb
         if not args.no_parity:
             ok = parity_all_outputs(res, cpu_out, offsets, uniq)
             out["parity_vs_oracle"] = {"all_equal": all(ok.values()), "outputs": ok}
-    if world > 1 and not args.no_parity:
+    if args.full and world > 1 and not args.no_parity:
         # every rank checks its own shard (a bounded prefix of its batch) against the
         # restatement, after the timed region
         out["parity_ranks"] = gather_ranks(rank_parity(res, offsets, sid, prob, rel, conf, present, uniq,
@@ -469,7 +531,7 @@ SECONDARY = (("c3", "c3", 20, 3, 1.0, {}), ("c3_fresh", "c3", 20, 3, 0.5, {"fres
 def run_secondary(args, world, rank) -> dict:
     """The other BASELINE.json configs, each timed exactly like its own ``--config`` line
     (reduced steps, same CPU baseline and full-size parity), summarised under the headline
-    line so the default run measures every config.  N = 1 only: configs 4 and 5 exchange
+    line so the --full run measures every config.  N = 1 only: configs 4 and 5 exchange
     per-source flags / per-agent counts over RCCL when N > 1 (``--config c4|c5 --gpus N``)."""
     import copy
     import gc
@@ -480,6 +542,7 @@ def run_secondary(args, world, rank) -> dict:
     for line, cfg, steps, warmup, ramp, extra in SECONDARY:
         a2 = copy.copy(args)
         a2.config, a2.steps, a2.warmup, a2.prewarm_s, a2.mode = cfg, steps, warmup, ramp, None
+        a2.dump_outputs = None
         for k, v in extra.items():
             setattr(a2, k, v)
         t0 = time.perf_counter()
@@ -530,6 +593,8 @@ def main(argv=None):
     args = parse(argv)
     if args.mode == "mfma" and args.config != "c5":
         raise SystemExit("bench.py: --mode mfma is the config-5 matrix-core pass (--config c5)")
+    if args.dump_outputs and (args.config != "c2" or args.stub or args.shard):
+        raise SystemExit("bench.py: --dump-outputs writes the headline (--config c2) outputs only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args, argv))
     world, rank, _ = dist_setup(args)
@@ -545,7 +610,7 @@ def main(argv=None):
         out = run_extra(args, world, rank)
     else:
         out = bench_c2(args, world, rank)
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             out["secondary"] = run_secondary(args, world, rank)
     if rank == 0:
         if isinstance(out.get("roofline"), dict):  # how avg_launch_ms was taken
