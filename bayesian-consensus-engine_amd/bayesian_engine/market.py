@@ -321,6 +321,59 @@ class CrossMarketAggregator:
             results[sid] = SourcePerformance(sid, t, c, w, c / (c + w) if (c + w) > 0 else 0.5, market_lists[i])
         return results
 
+    def reestimate_sources(self, iters: int = 10, patterns: Optional[List[str]] = None,
+                           prior: float = 0.5) -> Dict[str, SourcePerformance]:
+        """Learned source reliabilities over every market that has signals, resolved or not:
+        ``iters`` rounds of consensus <-> reliability (batch.reestimate_csr), every source
+        starting at ``prior``.  A RESOLVED market with an outcome is scored against that outcome,
+        as summarize_sources does; any other market against its own consensus vote
+        (``consensus >= 0.5``), and is left out of a round in which it has no consensus or holds
+        a probability outside [0, 1].  Sources are interned in sorted() order, so every
+        consensus sums in compute_consensus's order (core.py:103).  ``reliability`` is the
+        weight after the last round; the counts and market lists are the last round's, laid
+        out as summarize_sources lays them out."""
+        markets = [m for m in self._store.list_markets() if m.signals]
+        if patterns:
+            markets = [m for m in markets if any(m.id.matches(p) for p in patterns)]
+        results: Dict[str, SourcePerformance] = {}
+        if not markets:
+            return results
+        rank = batch.intern(signal["sourceId"] for m in markets for signal in m.signals)
+        offsets = [0]
+        sid_list: List[int] = []
+        prob_list: List[float] = []
+        known: List[int] = []
+        for market in markets:
+            for signal in market.signals:
+                prob = signal.get("probability", 0.5)
+                if not isinstance(prob, (int, float)):
+                    prob >= 0.5  # noqa: B015  -- the reference's TypeError (market.py:299)
+                sid_list.append(rank[signal["sourceId"]])
+                prob_list.append(float(prob))
+            offsets.append(len(sid_list))
+            resolved = market.status == MarketStatus.RESOLVED and market.outcome is not None
+            known.append((1 if market.outcome else 0) if resolved else -1)
+        N.require_gpu()
+        dev = N.device()
+        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        plan = batch.ReestimateCsrPlan.build(T(np.array(offsets, np.int64)), T(np.array(sid_list, np.int32)),
+                                             T(np.array(prob_list, np.float64)), len(rank))
+        r = batch.reestimate_csr(plan, iters, w0=prior, known=T(np.array(known, np.int8)))
+        w = r.w.cpu().numpy()
+        correct = r.correct.cpu().numpy()
+        total = r.total.cpu().numpy()
+        outcome = r.outcome.cpu().numpy()
+        market_lists: Dict[str, List[str]] = {}
+        for market, o in zip(markets, outcome):
+            if o < 0:
+                continue
+            for signal in market.signals:
+                market_lists.setdefault(signal["sourceId"], []).append(str(market.id))
+        for sid, lst in market_lists.items():
+            c, t = int(correct[rank[sid]]), int(total[rank[sid]])
+            results[sid] = SourcePerformance(sid, t, c, t - c, float(w[rank[sid]]), lst)
+        return results
+
     def summarize_category(self, category: str) -> Dict[str, Any]:
         markets = self._store.list_markets(pattern=f"{category}:*")
         resolved = [m for m in markets if m.status == MarketStatus.RESOLVED]

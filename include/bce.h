@@ -341,6 +341,51 @@ int bce_reestimate_consensus_votes_mfma(const double* P, int64_t A, int64_t M, i
                                         int64_t scratch_bytes, void* stream);
 int64_t bce_reestimate_mfma_scratch_bytes(int64_t M);
 
+/* ---- re-estimation over a ragged CSR batch: compile once, then iterate --------------
+ * The same composition as above -- compute_consensus with source_reliability = w
+ * (core.py:103-144), then the summarize_sources counts (market.py:293-304) and
+ * w_new = correct / total (market.py:309-310) -- for CSR markets with any number of signals
+ * per source, duplicates included.  Everything that depends on (offsets, sid, prob) alone is
+ * compiled into one entry per unique (market, source) pair, in (market, ascending sid)
+ * order (core.py:103); a round reads the entries only, each array at most once per kernel.
+ *
+ * bce_reestimate_csr_compile: the caller sorts the n_signals keys market * n_sources + sid
+ * (sid clamped to [0, n_sources)) with a STABLE sort -> key (sorted) and perm (signal index
+ * of each sorted position), and marks the n_entries runs of equal keys in
+ * group_start[n_entries + 1] (group_start[n_entries] = n_signals).  Per entry e the kernel
+ * writes usid[e], emarket[e], avg[e] = (0.0 + p1 + p2 ...) / count over the run's signals in
+ * input order (core.py:115-116), votes[e] = n_ge << 16 | n_lt with n_ge = #{p >= 0.5}
+ * (market.py:298-299; each count <= 65535, n_markets < 2^31), and sets bad[market] = 1 when
+ * a signal of the run has p < 0 or p > 1 (core.py:59-60; NaN passes).  bad must be zeroed
+ * first.  A raw sid outside [0, n_sources) raises the device fault word (bce_fault_check).
+ *
+ * bce_reestimate_csr_consensus: uoffsets[n_markets + 1] = the entry range of every market.
+ * consensus[m] = sum avg * w[usid] / sum w[usid], both left to right (core.py:120,135-138);
+ * null[m] = the market is empty or its weights sum to 0 (core.py:88,131; consensus 0.0);
+ * outcome[m] = known[m] where known (nullable) is >= 0 (a resolved market, market.py:280),
+ * else -1 (skip) for a null or bad market, else consensus >= 0.5.
+ *
+ * bce_reestimate_csr_agreement: for every entry of a market with outcome >= 0,
+ * total[usid] += n_ge + n_lt and correct[usid] += (outcome ? n_ge : n_lt)
+ * (market.py:293-302).  int64 atomics, exact and order-free; ACCUMULATED (zero them first),
+ * so the shards of a batch can add into one pair of count vectors.
+ *
+ * bce_reestimate_csr_weights: w[s] = correct[s] / total[s], 0.5 where total[s] == 0
+ * (market.py:309-310). */
+int bce_reestimate_csr_compile(const int64_t* group_start, int64_t n_entries, const int64_t* perm,
+                               const int64_t* key, int64_t n_signals, const int32_t* sid, const double* prob,
+                               int32_t n_sources, int64_t n_markets, int32_t* usid, double* avg,
+                               int32_t* votes, int32_t* emarket, uint8_t* bad, void* stream);
+int bce_reestimate_csr_consensus(const int64_t* uoffsets, int64_t n_markets, const int32_t* usid,
+                                 const double* avg, const uint8_t* bad, const int8_t* known, const double* w,
+                                 int32_t n_sources, double* consensus, uint8_t* null_out, int8_t* outcome,
+                                 void* stream);
+int bce_reestimate_csr_agreement(int64_t n_entries, const int32_t* usid, const int32_t* votes,
+                                 const int32_t* emarket, const int8_t* outcome, int64_t n_markets,
+                                 int32_t n_sources, int64_t* correct, int64_t* total, void* stream);
+int bce_reestimate_csr_weights(int64_t n_sources, const int64_t* correct, const int64_t* total, double* w,
+                               void* stream);
+
 /* ---- JSONL front end (host C++, no GPU): SURVEY §8 f2 -----------------------------------
  *
  * Replaces, for a batch: cli._cmd_consensus_legacy / _cmd_consensus (cli.py:25-52,163-174)
