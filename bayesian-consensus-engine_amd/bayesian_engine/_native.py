@@ -92,6 +92,9 @@ _SIGS = {
     "bce_reestimate_csr_consensus": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "bce_reestimate_csr_agreement": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "bce_reestimate_csr_weights": (C.c_int, [_i64, _vp, _vp, _vp, _vp]),
+    "bce_settle_compile": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "bce_settle_apply": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp,
+                                   _i64, _f64, _f64, _vp, _vp]),
     "bce_namespace_resolve": (C.c_int, [_i64] + [_vp] * 12 + [_i32, _i64, _f64, _f64, _f64, _f64, _i32,
                                                                _vp, _vp, _vp, _vp]),
     "bce_aggregate_groups": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

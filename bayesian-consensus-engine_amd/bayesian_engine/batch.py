@@ -127,6 +127,10 @@ class ReliabilityTable:
         rel = self.view(now_us) if now_us is not None else self.rel
         return SourceTable.from_arrays(rel, self.conf, None if all_present else self.present, self.names)
 
+    def settle(self, plan: "SettlePlan", now_us: int, **kw) -> None:
+        """:func:`settle` in place on this table (a domain or the global scope)."""
+        settle(plan, self.rel, self.conf, self.t_us, self.present, now_us, **kw)
+
 
 # ---------------------------------------------------------------------------------------
 # consensus
@@ -333,7 +337,8 @@ def outcome_update(rel: torch.Tensor, conf: torch.Tensor, t_us: torch.Tensor, pr
                    default_conf: float = DEFAULT_CONFIDENCE) -> None:
     """In-place update_reliability math for every participant (reliability.py:142-183).
 
-    flags u8[S]: bit0 participates, bit1 correct (at most one outcome per source per call).
+    flags u8[S]: bit0 participates, bit1 correct (at most one outcome per source per call;
+    :func:`settle` applies a whole batch of resolved markets, any number per source).
     """
     L = N.require_gpu()
     N.check(L.bce_outcome_update(rel.numel(), N.ptr(rel), N.ptr(conf), N.ptr(t_us), N.ptr(present),
@@ -837,3 +842,168 @@ def reestimate_csr(plan: ReestimateCsrPlan, iters: int, w0: float = 0.5, w: Opti
         res = (torch.zeros(M, dtype=torch.float64, device=dev), torch.zeros(M, dtype=torch.uint8, device=dev),
                torch.full((M,), -1, dtype=torch.int8, device=dev))
     return ReestimateCsrResult(w, res[0], res[1], res[2], correct, total, hist)
+
+
+# ---------------------------------------------------------------------------------------
+# settlement: a batch of resolved markets into one scope of the reliability table
+# ---------------------------------------------------------------------------------------
+# Chains of at least SETTLE_LONG_MIN bits are cut into chunks of SETTLE_CHUNK_BITS bits that run
+# in parallel (settle_long_kernel): the best point of the measured grid (DESIGN.md §4.14,
+# measurements/settle.txt).  2**62 disables the long path.
+SETTLE_LONG_MIN = 256
+SETTLE_CHUNK_BITS = 256
+SETTLE_LONG_OFF = 1 << 62
+
+
+def _settle_order(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
+                  n_sources: int):
+    """The integer half of :meth:`SettlePlan.build` (any device, no kernel): checks the shapes,
+    lists the signals of markets with ``outcome >= 0`` in CSR order and sorts them by ``sid``
+    keeping that order inside a source.  Returns ``(market, perm, key, total, start, order,
+    lens_desc)``: the market of every signal (int32[N]), the signal index and clamped sid of every
+    sorted position, the chain length and bit offset per source, the touched sources longest
+    chain first and their lengths."""
+    M = offsets.numel() - 1
+    Nsig = sid.numel()
+    if M < 0 or offsets.dim() != 1:
+        raise ValueError("offsets must be a 1-D tensor of n_markets + 1 entries")
+    if M >= (1 << 31):
+        raise ValueError(f"settle: {M} markets (the signal-to-market map is int32)")
+    try:
+        S = int(n_sources)
+    except (TypeError, ValueError):
+        raise ValueError(f"n_sources must be in [1, 2^31) (got {n_sources!r})") from None
+    if not 0 < S < (1 << 31):
+        raise ValueError(f"n_sources must be in [1, 2^31) (got {n_sources})")
+    if prob.numel() != Nsig:
+        raise ValueError("sid and prob differ in length")
+    if outcome.dtype != torch.int8:
+        raise ValueError(f"outcome must be int8 (-1 unresolved, 0, 1), got {outcome.dtype}")
+    if outcome.dim() != 1 or outcome.numel() != M:
+        raise ValueError(f"outcome must have one entry per market ({M}), got {tuple(outcome.shape)}")
+    dev = offsets.device
+    offsets = offsets.to(torch.int64)
+    lens = offsets[1:] - offsets[:-1]
+    if M and (int(offsets[0]) != 0 or int(offsets[-1]) != Nsig or int(lens.min()) < 0):
+        raise ValueError("offsets must rise from 0 to len(sid)")
+    if M == 0 and Nsig:
+        raise ValueError("offsets must rise from 0 to len(sid)")
+    i64 = dict(dtype=torch.int64, device=dev)
+    market = torch.repeat_interleave(torch.arange(M, **i64), lens, output_size=Nsig)
+    idx = torch.nonzero(outcome[market] >= 0).flatten()  # ascending: market, then position
+    key = sid[idx].to(torch.int32).clamp(0, S - 1)
+    key, p = torch.sort(key, stable=True)
+    perm = idx[p]
+    total = torch.bincount(key, minlength=S).to(torch.int64)
+    start = torch.zeros(S + 1, **i64)
+    start[1:] = torch.cumsum(total, 0)
+    lens_desc, order = torch.sort(total, descending=True, stable=True)
+    T = int((total > 0).sum())
+    return (market.to(torch.int32), perm, key, total, start, order[:T].to(torch.int32).contiguous(),
+            lens_desc[:T].cpu().numpy())
+
+
+@dataclass
+class SettlePlan:
+    """A batch of resolved markets compiled for :func:`settle`: one correctness bit per signal
+    of a market with ``outcome >= 0`` -- ``(probability >= 0.5) == outcome``, market.py:298-301 --
+    the bits of one source contiguous and in the reference's loop order (market ascending, then
+    position in the market).  ``bits`` u64[ceil(n_bits / 64)] (as int64), ``start`` int64[S+1]
+    (bit offset of every source's chain), ``order`` int32[T] (the touched sources, longest chain
+    first), ``total`` / ``correct`` int64[S] (chain length and its popcount: the
+    summarize_sources counts, market.py:293-304).  Reusable: the same plan settles the domain and
+    the global scope."""
+
+    bits: torch.Tensor
+    start: torch.Tensor
+    order: torch.Tensor
+    total: torch.Tensor
+    correct: torch.Tensor
+    n_bits: int
+    n_sources: int
+    lens_desc: np.ndarray   # host: chain lengths in ``order``
+    _chunks: Optional[dict] = None  # (long_min, chunk_bits) -> (n_long, chunk_start, n_chunks)
+
+    @property
+    def n_touched(self) -> int:
+        return int(self.order.numel())
+
+    @classmethod
+    def build(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
+              n_sources: int, check: bool = True) -> "SettlePlan":
+        """Compile ``(offsets, sid, prob)`` with ``outcome`` int8[M] (-1 unresolved, 0, 1).  The
+        ordering is a stable torch sort by ``sid``; the bits and ``correct`` are one launch of
+        bce_settle_compile.  Synchronises (once per batch).  A ``sid`` outside ``[0, n_sources)``
+        is clamped and raises :class:`BCEError` like ``consensus(check=True)`` (``check=False``
+        leaves the device fault word for a later ``_native.check_faults``); 2^31 markets or
+        sources, an ``outcome`` of the wrong length or dtype, ``ValueError``."""
+        market, perm, key, total, start, order, lens_desc = _settle_order(offsets, sid, prob, outcome, n_sources)
+        M, Nsig, S, Np = offsets.numel() - 1, sid.numel(), int(n_sources), perm.numel()
+        dev = offsets.device
+        L = N.require_gpu()
+        bits = torch.zeros(max((Np + 63) // 64, 1), dtype=torch.int64, device=dev)
+        correct = torch.zeros(S, dtype=torch.int64, device=dev)
+        sid = sid.to(torch.int32).contiguous()
+        prob = prob.to(torch.float64).contiguous()
+        outcome = outcome.contiguous()
+        N.check(L.bce_settle_compile(N.ptr(perm), Np, N.ptr(key), N.ptr(sid), N.ptr(prob), N.ptr(market), Nsig,
+                                     N.ptr(outcome), M, S, N.ptr(bits), N.ptr(correct), N.stream(dev)),
+                "bce_settle_compile")
+        if check:
+            N.check_faults(dev, "settle compile")
+        return cls(bits, start, order, total, correct, Np, S, lens_desc)
+
+    def chunks(self, long_min: int, chunk_bits: int):
+        """``(n_long, chunk_start, n_chunks)`` of the long path for these parameters (cached)."""
+        long_min, chunk_bits = int(long_min), int(chunk_bits)
+        if long_min < 1:
+            raise ValueError(f"long_min must be >= 1 (got {long_min})")
+        if chunk_bits < 64:
+            raise ValueError(f"chunk_bits must be >= 64 (got {chunk_bits})")
+        if self._chunks is None:
+            self._chunks = {}
+        hit = self._chunks.get((long_min, chunk_bits))
+        if hit is None:
+            ld = self.lens_desc
+            n_long = int(np.searchsorted(-ld, -long_min, side="right"))  # descending: the leading >= long_min
+            cs = np.zeros(n_long + 1, np.int64)
+            cs[1:] = np.cumsum((ld[:n_long] + chunk_bits - 1) // chunk_bits)
+            dev = self.order.device
+            hit = (n_long, torch.from_numpy(cs).to(dev) if n_long else None, int(cs[-1]))
+            self._chunks[(long_min, chunk_bits)] = hit
+        return hit
+
+
+def settle(plan: SettlePlan, rel: torch.Tensor, conf: torch.Tensor, t_us: torch.Tensor,
+           present: Optional[torch.Tensor], now_us: int, *, long_min: Optional[int] = None,
+           chunk_bits: Optional[int] = None, default_rel: float = DEFAULT_RELIABILITY,
+           default_conf: float = DEFAULT_CONFIDENCE) -> None:
+    """update_reliability for every signal of the compiled batch, in the reference's order, in
+    place on one scope table (reliability.py:142-233 per signal; bit-exact, there is no fast
+    mode).  Every touched source starts from its row -- the cold defaults where ``present`` is 0
+    -- takes one update per bit of its chain, and gets ``t_us = now_us`` and ``present = 1``;
+    rows of other sources are not written.
+
+    The scope is a domain (``__domain__:<d>``) or the global table, where one row per source
+    collects the updates of all its markets.  Market-level scope is NOT handled here: its rows
+    are keyed by (source, market), so every market has rows of its own and a chain is only a
+    market's duplicate signals.
+
+    ``long_min`` / ``chunk_bits`` (defaults SETTLE_LONG_MIN / SETTLE_CHUNK_BITS): chains of at
+    least ``long_min`` bits run one worker per ``chunk_bits`` bits (settle_long_kernel); the
+    result does not depend on either.  ``long_min=2**62`` walks every chain by one lane."""
+    L = N.require_gpu()
+    S = plan.n_sources
+    assert rel.dtype == torch.float64 and conf.dtype == torch.float64 and t_us.dtype == torch.int64, \
+        "rel / conf must be fp64 and t_us int64"
+    assert rel.numel() == S and conf.numel() == S and t_us.numel() == S, "the table must have n_sources rows"
+    assert present is None or (present.dtype == torch.uint8 and present.numel() == S), "present must be u8[n_sources]"
+    long_min = SETTLE_LONG_MIN if long_min is None else long_min
+    chunk_bits = SETTLE_CHUNK_BITS if chunk_bits is None else chunk_bits
+    n_long, chunk_start, n_chunks = plan.chunks(long_min, chunk_bits)
+    dev = rel.device
+    snap = torch.empty((n_long, 2), dtype=torch.float64, device=dev) if n_long else None
+    N.check(L.bce_settle_apply(N.ptr(plan.bits), plan.n_bits, N.ptr(plan.start), N.ptr(plan.order), plan.n_touched,
+                               n_long, N.ptr(chunk_start), n_chunks, int(chunk_bits), S, N.ptr(rel), N.ptr(conf),
+                               N.ptr(t_us), N.ptr(present), int(now_us), float(default_rel), float(default_conf),
+                               N.ptr(snap), N.stream(dev)), "bce_settle_apply")

@@ -374,6 +374,22 @@ class CrossMarketAggregator:
             results[sid] = SourcePerformance(sid, t, c, t - c, float(w[rank[sid]]), lst)
         return results
 
+    def settle_resolved(self, store, domain: Optional[str] = None, update_global: bool = False,
+                        patterns: Optional[List[str]] = None, dry_run: bool = False):
+        """Commit every RESOLVED market with an outcome to the reliability store: the markets
+        summarize_sources counts over, in the same order (list_markets, the pattern filter, then
+        ``outcome is not None``), passed as ``(signals, outcome)`` to
+        ``store.settle_markets`` (:class:`NamespacedReliabilityStore`), which applies
+        ``update_reliability`` per signal at the domain or global scope in one compiled batch.
+        Market-level scope is not offered: its rows are keyed by (source, market).  Returns the
+        store's summary: the records and the ``total`` / ``correct`` counts per source."""
+        markets = self._store.list_markets(status=MarketStatus.RESOLVED)
+        if patterns:
+            markets = [m for m in markets if any(m.id.matches(p) for p in patterns)]
+        markets = [m for m in markets if m.outcome is not None]
+        return store.settle_markets([(m.signals, m.outcome) for m in markets], domain=domain,
+                                    update_global=update_global, dry_run=dry_run)
+
     def summarize_category(self, category: str) -> Dict[str, Any]:
         markets = self._store.list_markets(pattern=f"{category}:*")
         resolved = [m for m in markets if m.status == MarketStatus.RESOLVED]

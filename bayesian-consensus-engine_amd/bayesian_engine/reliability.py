@@ -16,7 +16,9 @@ Bulk paths for millions of sources:
 * :meth:`SQLiteReliabilityStore.decayed_view` -- ``get_reliability(apply_decay=True)``
   for every row of a scope in one launch;
 * :meth:`SQLiteReliabilityStore.apply_outcomes` -- one outcome per source: one GPU launch,
-  then one ``executemany`` upsert in a single transaction (``dry_run`` = no write-back).
+  then one ``executemany`` upsert in a single transaction (``dry_run`` = no write-back);
+* :meth:`SQLiteReliabilityStore.settle` -- any number of outcomes per source: a compiled batch
+  of resolved markets (``batch.SettlePlan``) applied to one domain or global scope.
 """
 from __future__ import annotations
 
@@ -218,6 +220,35 @@ class SQLiteReliabilityStore:
                 self._conn.execute("BEGIN")
                 self._conn.executemany(_UPSERT_SQL, [(n, market_id, float(rel[i]), float(conf[i]), stamp)
                                                      for i, n in enumerate(names)])
+        return out
+
+    def settle(self, market_id: str, names: Sequence[str], plan: "batch.SettlePlan", dry_run: bool = False,
+               now: Optional[datetime] = None) -> Dict[str, ReliabilityRecord]:
+        """update_reliability for every signal of a compiled batch of resolved markets
+        (:class:`batch.SettlePlan` over the rank space ``names``), any number of outcomes per
+        source, in the reference's loop order: one load_table, the chain kernels, then one
+        ``executemany`` upsert of the touched rows in a single transaction.  ``market_id`` is a
+        domain (``__domain__:<d>``) or the global scope key; market-level rows are keyed by
+        (source, market) and are not what a plan over many markets describes.  Returns the
+        touched sources' records."""
+        names = list(names)
+        if len(names) != plan.n_sources:
+            raise ValueError(f"the plan ranks {plan.n_sources} sources, names has {len(names)}")
+        table = self.load_table(market_id, names, device=plan.order.device)
+        now_us = dt_to_us(now or datetime.now(timezone.utc))
+        table.settle(plan, now_us)
+        touched = plan.order.cpu().numpy()
+        rel = table.rel.cpu().numpy()
+        conf = table.conf.cpu().numpy()
+        N.check_faults(plan.order.device, "settle")
+        stamp = us_to_iso(now_us)
+        out = {names[i]: ReliabilityRecord(names[i], market_id, float(rel[i]), float(conf[i]), stamp)
+               for i in sorted(int(x) for x in touched)}
+        if not dry_run and out:
+            with self._conn:  # one transaction
+                self._conn.execute("BEGIN")
+                self._conn.executemany(_UPSERT_SQL, [(r.source_id, market_id, r.reliability, r.confidence, stamp)
+                                                     for r in out.values()])
         return out
 
     def fetch_pairs(self, pairs: Sequence[tuple]) -> Dict[tuple, tuple]:

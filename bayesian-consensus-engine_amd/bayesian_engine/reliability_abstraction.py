@@ -28,7 +28,7 @@ from .reliability import SQLiteReliabilityStore
 from .timeutil import NO_TIMESTAMP, dt_to_us, iso_to_us
 
 __all__ = ["ReliabilityNamespace", "NamespacedReliabilityRecord", "ReliabilityProvider",
-           "NamespacedReliabilityStore"]
+           "NamespacedReliabilityStore", "SettleSummary"]
 
 
 class ReliabilityNamespace(str, Enum):
@@ -50,6 +50,18 @@ class NamespacedReliabilityRecord:
     confidence: float
     updated_at: str
     is_fallback: bool
+
+
+@dataclass(frozen=True)
+class SettleSummary:
+    """What :meth:`NamespacedReliabilityStore.settle_markets` did, per touched source: the record
+    of the settled scope, the global record when it was updated as well, and the
+    summarize_sources counts of the batch (signals in resolved markets, and how many agreed)."""
+
+    records: dict
+    global_records: dict
+    total: dict
+    correct: dict
 
 
 @runtime_checkable
@@ -191,6 +203,64 @@ class NamespacedReliabilityStore:
         code = scope.cpu().numpy()
         chosen = [stamps[c][i] if c < 3 else "" for i, c in enumerate(code)]
         return table, scope, chosen
+
+    def settle_markets(self, markets: Sequence[tuple], domain: Optional[str] = None, update_global: bool = False,
+                       dry_run: bool = False, now: Optional[datetime] = None) -> "SettleSummary":
+        """``update_reliability(sid, correct, domain=domain, update_global=update_global)`` for
+        every signal of every resolved market, in list order, as ONE compiled batch.
+
+        ``markets`` is a sequence of ``(signals, outcome)``: the reference's signal dicts and the
+        market's outcome (``None``: the market is skipped); ``correct`` is ``(probability >= 0.5)
+        == outcome`` with a missing probability read as 0.5 (market.py:298-301).  Sources are
+        interned in sorted() order, one :class:`batch.SettlePlan` is built and applied to the
+        ``__domain__:<domain>`` scope, or to ``__global__`` when ``domain`` is None; with
+        ``update_global`` and a domain the same plan is applied a second time to ``__global__``
+        (reliability_abstraction.py:225-229).  Market-level scope is out of scope here: there the
+        rows are keyed by (source, market), every market has rows of its own and a chain is only
+        a market's duplicate signals -- use update_reliability(market_id=...).  ``dry_run``
+        computes the records and writes nothing."""
+        markets = [(list(signals), outcome) for signals, outcome in markets]
+        rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
+        names = list(rank)
+        offsets = [0]
+        sid_list: List[int] = []
+        prob_list: List[float] = []
+        outcome_list: List[int] = []
+        for signals, outcome in markets:
+            for s in signals:
+                prob = s.get("probability", 0.5)
+                if not isinstance(prob, (int, float)):
+                    prob >= 0.5  # noqa: B015  -- the reference's TypeError (market.py:299)
+                sid_list.append(rank[s["sourceId"]])
+                prob_list.append(float(prob))
+            offsets.append(len(sid_list))
+            outcome_list.append(-1 if outcome is None else (1 if outcome else 0))
+        if domain:
+            namespace, value, target = ReliabilityNamespace.DOMAIN, domain, f"__domain__:{domain}"
+        else:
+            namespace, value, target = ReliabilityNamespace.GLOBAL, "global", self.GLOBAL_MARKET_ID
+        if not names:
+            return SettleSummary({}, {}, {}, {})
+        N.require_gpu()
+        dev = N.device()
+        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        plan = batch.SettlePlan.build(T(np.array(offsets, np.int64)), T(np.array(sid_list, np.int32)),
+                                      T(np.array(prob_list, np.float64)), T(np.array(outcome_list, np.int8)),
+                                      len(names))
+        now = now or datetime.now(timezone.utc)
+        recs = self._store.settle(target, names, plan, dry_run=dry_run, now=now)
+        records = {sid: NamespacedReliabilityRecord(sid, namespace, value, r.reliability, r.confidence,
+                                                    r.updated_at, False) for sid, r in recs.items()}
+        global_records = {}
+        if update_global and namespace != ReliabilityNamespace.GLOBAL:
+            grecs = self._store.settle(self.GLOBAL_MARKET_ID, names, plan, dry_run=dry_run, now=now)
+            global_records = {sid: NamespacedReliabilityRecord(sid, ReliabilityNamespace.GLOBAL, "global",
+                                                               r.reliability, r.confidence, r.updated_at, False)
+                              for sid, r in grecs.items()}
+        total = plan.total.cpu().numpy()
+        correct = plan.correct.cpu().numpy()
+        return SettleSummary(records, global_records, {sid: int(total[rank[sid]]) for sid in records},
+                             {sid: int(correct[rank[sid]]) for sid in records})
 
     def get_reliability_many(self, names: Sequence[str], market_id: Optional[str] = None,
                              domain: Optional[str] = None, apply_decay: bool = True,

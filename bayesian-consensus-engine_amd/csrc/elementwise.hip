@@ -10,6 +10,7 @@
 #include "bce_device.hpp"
 #include "bce_internal.hpp"
 #include "glibc_pow.hpp"
+#include "reliability_update.hpp"
 
 #pragma clang fp contract(off)
 
@@ -35,14 +36,7 @@ __device__ __forceinline__ double decayed(double r, int64_t t_us, const DecayCon
   return py_max(k.min_rel, py_min(1.0, d));
 }
 
-// reliability.py:163-173 for one participant.
-__device__ __forceinline__ void update_one(double& r, double& c, bool correct) {
-  const double direction = correct ? 1.0 : -1.0;
-  const double raw = 0.15 * direction;                      // _BASE_LEARNING_RATE
-  const double capped = py_max(-0.10, py_min(0.10, raw));   // MAX_UPDATE_STEP
-  r = py_max(0.0, py_min(1.0, r + capped));
-  c = py_min(1.0, c + (1.0 - c) * 0.10);
-}
+// update_one (reliability.py:163-173 for one participant) lives in reliability_update.hpp.
 
 __global__ __launch_bounds__(256) void decay_view_kernel(int64_t n, const double* __restrict__ rel,
                                                          const int64_t* __restrict__ t_us,

@@ -386,6 +386,40 @@ int bce_reestimate_csr_agreement(int64_t n_entries, const int32_t* usid, const i
 int bce_reestimate_csr_weights(int64_t n_sources, const int64_t* correct, const int64_t* total, double* w,
                                void* stream);
 
+/* ---- settlement: a batch of resolved markets into one scope of the reliability table ------
+ * Replaces the per-signal loop update_reliability(source, correct) over every signal of every
+ * resolved market (reliability.py:142-233, reliability_abstraction.py:190-240) with
+ * correct = (probability >= 0.5) == outcome (market.py:298-301), bit for bit: a source's updates
+ * are applied as one chain in the reference's loop order (market ascending, then position).
+ *
+ * bce_settle_compile: the caller lists the n_part signals of markets with outcome >= 0 in CSR
+ * order, sorts them by sid (clamped to [0, n_sources)) with a STABLE sort -> key (sorted sids)
+ * and perm (signal index of each sorted position), and gives market[n_signals] (the market of
+ * every signal).  The kernel packs one correctness bit per sorted position into
+ * bits[ceil(n_part / 64)] (bit j % 64 of word j / 64; NaN >= 0.5 is false, a probability outside
+ * [0, 1] is not screened) and ADDS every source's set bits into correct[n_sources] (zero it
+ * first).  A raw sid outside [0, n_sources), or a perm / market entry outside the batch, raises
+ * the device fault word (bce_fault_check).
+ *
+ * bce_settle_apply: in place on rel / conf / t_us / present (nullable: every row exists) of one
+ * scope.  start[n_sources + 1] = the bit offset of every source's chain, order[n_touched] = the
+ * sources with a chain, longest first.  Every such source starts from its row, or from
+ * (default_rel, default_conf) where present is 0 (reliability.py:133-140), takes one update per
+ * bit (reliability.py:163-173), and gets t_us = now_us, present = 1; other rows are not
+ * written.  The first n_long sources of order are cut into chunks of chunk_bits (>= 64) bits,
+ * chunk_start[n_long + 1] = the running chunk count, n_chunks = its last entry; they run one
+ * worker per chunk (a run of 11 equal bits pins the reliability to exactly 1.0 or 0.0, so a
+ * worker can start behind one) from snap[2 * n_long] (16-byte aligned scratch).  n_long = 0
+ * walks every chain by one lane. */
+int bce_settle_compile(const int64_t* perm, int64_t n_part, const int32_t* key, const int32_t* sid,
+                       const double* prob, const int32_t* market, int64_t n_signals, const int8_t* outcome,
+                       int64_t n_markets, int32_t n_sources, uint64_t* bits, int64_t* correct, void* stream);
+int bce_settle_apply(const uint64_t* bits, int64_t n_bits, const int64_t* start, const int32_t* order,
+                     int64_t n_touched, int64_t n_long, const int64_t* chunk_start, int64_t n_chunks,
+                     int64_t chunk_bits, int32_t n_sources, double* rel, double* conf, int64_t* t_us,
+                     uint8_t* present, int64_t now_us, double default_rel, double default_conf, double* snap,
+                     void* stream);
+
 /* ---- JSONL front end (host C++, no GPU): SURVEY §8 f2 -----------------------------------
  *
  * Replaces, for a batch: cli._cmd_consensus_legacy / _cmd_consensus (cli.py:25-52,163-174)
