@@ -22,6 +22,7 @@ BCE_OK = 0
 MODE_EXACT = 0
 MODE_FAST = 1
 NBINS = 13  # include/bce.h BCE_NBINS
+PAIR_STORE, PAIR_NAMESPACED, PAIR_RAW = 0, 1, 2  # include/bce.h bce_pair_mode
 NO_TIMESTAMP = -(2**63)
 TB_LABELS = {0: "unanimous", 1: "weight_density", 2: "prediction_value_smallest", 3: "unanimous"}
 
@@ -97,6 +98,8 @@ _SIGS = {
                                    _i64, _f64, _f64, _vp, _vp]),
     "bce_namespace_resolve": (C.c_int, [_i64] + [_vp] * 12 + [_i32, _i64, _f64, _f64, _f64, _f64, _i32,
                                                                _vp, _vp, _vp, _vp]),
+    "bce_pair_resolve": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _i64] + [_vp] * 6 + [_i64, _i32] + [_vp] * 8 +
+                         [_i32, _i64, _f64, _f64, _f64, _f64, _i32] + [_vp] * 10),
     "bce_aggregate_groups": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

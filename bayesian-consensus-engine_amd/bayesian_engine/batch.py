@@ -676,10 +676,12 @@ def reestimate(P: torch.Tensor, iters: int, w0: float = 0.5, w: Optional[torch.T
 _RC_MAX_RUN = 65535  # signals of one source in one market: the votes are two 16-bit counts
 
 
-def _reestimate_csr_order(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, n_sources: int):
-    """The integer half of :meth:`ReestimateCsrPlan.build` (any device, no kernel): checks the
-    shapes, sorts the signals by (market, sid) keeping input order inside a pair, and returns
-    ``(key, perm, group_start, uoffsets)`` as bce_reestimate_csr_compile takes them."""
+def _reestimate_csr_order(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, n_sources: int,
+                          max_run: Optional[int] = _RC_MAX_RUN):
+    """The integer half of :meth:`ReestimateCsrPlan.build` and :meth:`PairPlan.build` (any device,
+    no kernel): checks the shapes, sorts the signals by (market, sid) keeping input order inside
+    a pair, and returns ``(key, perm, group_start, uoffsets)`` as bce_reestimate_csr_compile takes
+    them.  ``max_run`` bounds the signals of one source in one market (None: no bound)."""
     M = offsets.numel() - 1
     Nsig = sid.numel()
     S = int(n_sources)
@@ -709,7 +711,7 @@ def _reestimate_csr_order(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.
     start = torch.nonzero(first).flatten()
     E = start.numel()
     group_start = torch.cat([start, torch.tensor([Nsig], **i64)])
-    if E and int((group_start[1:] - group_start[:-1]).max()) > _RC_MAX_RUN:
+    if E and max_run is not None and int((group_start[1:] - group_start[:-1]).max()) > max_run:
         raise ValueError(f"reestimate_csr: a source has more than {_RC_MAX_RUN} signals in one market")
     per_market = torch.bincount(torch.div(key[start], S, rounding_mode="floor"), minlength=M)
     uoffsets = torch.zeros(M + 1, **i64)
@@ -985,9 +987,9 @@ def settle(plan: SettlePlan, rel: torch.Tensor, conf: torch.Tensor, t_us: torch.
     rows of other sources are not written.
 
     The scope is a domain (``__domain__:<d>``) or the global table, where one row per source
-    collects the updates of all its markets.  Market-level scope is NOT handled here: its rows
-    are keyed by (source, market), so every market has rows of its own and a chain is only a
-    market's duplicate signals.
+    collects the updates of all its markets.  Market-level scope, whose rows are keyed by
+    (source, market), is :func:`settle_pairs`: it runs this function over the batch's unique
+    pairs, where a chain is a market's duplicate signals of one source.
 
     ``long_min`` / ``chunk_bits`` (defaults SETTLE_LONG_MIN / SETTLE_CHUNK_BITS): chains of at
     least ``long_min`` bits run one worker per ``chunk_bits`` bits (settle_long_kernel); the
@@ -1007,3 +1009,285 @@ def settle(plan: SettlePlan, rel: torch.Tensor, conf: torch.Tensor, t_us: torch.
                                n_long, N.ptr(chunk_start), n_chunks, int(chunk_bits), S, N.ptr(rel), N.ptr(conf),
                                N.ptr(t_us), N.ptr(present), int(now_us), float(default_rel), float(default_conf),
                                N.ptr(snap), N.stream(dev)), "bce_settle_apply")
+
+
+# ---------------------------------------------------------------------------------------
+# market scope: the (source, market) rows of the store as a sparse table in HBM
+# ---------------------------------------------------------------------------------------
+@dataclass
+class PairTable:
+    """The market-scope rows of a batch of markets, CSR by market over the batch's market index:
+    ``poffsets`` int64[M+1] (the row range of every market), ``psid`` int32[P] (source ranks,
+    strictly ascending inside a market), ``rel`` / ``conf`` fp64[P], ``t_us`` int64[P]
+    (NO_TIMESTAMP where ``updated_at`` is falsy or unparseable), ``has`` u8[P] (``updated_at`` is
+    truthy: the ``if record.updated_at`` test).  Only rows that exist are stored."""
+
+    poffsets: torch.Tensor
+    psid: torch.Tensor
+    rel: torch.Tensor
+    conf: torch.Tensor
+    t_us: torch.Tensor
+    has: torch.Tensor
+    n_markets: int
+    n_sources: int
+
+    @property
+    def n_rows(self) -> int:
+        return int(self.psid.numel())
+
+    @classmethod
+    def empty(cls, n_markets: int, n_sources: int, device=None) -> "PairTable":
+        dev = device if device is not None else N.device()
+        z = lambda dt: torch.zeros(0, dtype=dt, device=dev)  # noqa: E731
+        return cls(torch.zeros(int(n_markets) + 1, dtype=torch.int64, device=dev), z(torch.int32),
+                   z(torch.float64), z(torch.float64), z(torch.int64), z(torch.uint8), int(n_markets),
+                   int(n_sources))
+
+    @classmethod
+    def from_rows(cls, market: torch.Tensor, sid: torch.Tensor, rel: torch.Tensor, conf: torch.Tensor,
+                  t_us: torch.Tensor, has: torch.Tensor, n_markets: int, n_sources: int) -> "PairTable":
+        """Rows in any order (tensors of one device, CPU included: torch only, no kernel) sorted
+        into the table.  A duplicate (market, sid), or an index outside the batch, ``ValueError``."""
+        M, S = int(n_markets), int(n_sources)
+        if M < 0 or M >= (1 << 31):
+            raise ValueError(f"n_markets must be in [0, 2^31) (got {n_markets})")
+        if not 0 < S < (1 << 31):
+            raise ValueError(f"n_sources must be in [1, 2^31) (got {n_sources})")
+        P = market.numel()
+        if not all(x.numel() == P for x in (sid, rel, conf, t_us, has)):
+            raise ValueError("the row arrays differ in length")
+        dev = market.device
+        if P == 0:
+            return cls.empty(M, S, dev)
+        mk = market.to(torch.int64)
+        sd = sid.to(torch.int64)
+        if int(mk.min()) < 0 or int(mk.max()) >= M:
+            raise ValueError("a row's market index is outside [0, n_markets)")
+        if int(sd.min()) < 0 or int(sd.max()) >= S:
+            raise ValueError("a row's source rank is outside [0, n_sources)")
+        key, perm = torch.sort(mk * S + sd)
+        if P > 1 and bool((key[1:] == key[:-1]).any()):
+            raise ValueError("duplicate (market, sid) row")
+        poffsets = torch.zeros(M + 1, dtype=torch.int64, device=dev)
+        poffsets[1:] = torch.cumsum(torch.bincount(mk, minlength=M), 0)
+        return cls(poffsets, sd[perm].to(torch.int32), rel.to(torch.float64)[perm].contiguous(),
+                   conf.to(torch.float64)[perm].contiguous(), t_us.to(torch.int64)[perm].contiguous(),
+                   has.to(torch.uint8)[perm].contiguous(), M, S)
+
+
+@dataclass
+class PairPlan:
+    """A CSR batch compiled over its unique (market, source) pairs ("entries"), in (market,
+    ascending sid) order -- the order compute_consensus sums in (core.py:103): ``uoffsets``
+    int64[M+1] (the entry range of every market), ``usid`` int32[E] (the source of every entry),
+    ``emarket`` int32[E], and ``esid`` int32[N]: every signal's entry index, which stands in for
+    its source rank wherever a per-pair table is gathered."""
+
+    uoffsets: torch.Tensor
+    usid: torch.Tensor
+    emarket: torch.Tensor
+    esid: torch.Tensor
+    n_markets: int
+    n_entries: int
+    n_sources: int
+
+    @classmethod
+    def build(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, n_sources: int) -> "PairPlan":
+        """Torch only (any device, CPU included), synchronises.  A ``sid`` outside ``[0,
+        n_sources)`` or 2^31 entries, ``ValueError``."""
+        S = int(n_sources)
+        if sid.numel() and (int(sid.min()) < 0 or int(sid.max()) >= S):
+            raise ValueError("a sid is outside [0, n_sources)")
+        key, perm, group_start, uoffsets = _reestimate_csr_order(offsets, sid, prob, n_sources, max_run=None)
+        M, Nsig, E = offsets.numel() - 1, sid.numel(), group_start.numel() - 1
+        if E >= (1 << 31):
+            raise ValueError(f"{E} unique (market, source) pairs (entries are indexed with int32)")
+        dev = offsets.device
+        ukey = key[group_start[:E]]
+        emarket = torch.div(ukey, S, rounding_mode="floor")
+        usid = (ukey - emarket * S).to(torch.int32)
+        runs = group_start[1:] - group_start[:-1]
+        esid = torch.empty(Nsig, dtype=torch.int32, device=dev)
+        esid[perm] = torch.repeat_interleave(torch.arange(E, dtype=torch.int32, device=dev), runs, output_size=Nsig)
+        return cls(uoffsets, usid, emarket.to(torch.int32), esid, M, E, S)
+
+
+@dataclass
+class PairResolveResult:
+    """Outputs of :func:`pair_resolve` (None where the mode does not produce them)."""
+
+    lb: Optional[torch.Tensor]       # int64[Q] lower-bound row of every entry (global row index)
+    matched: Optional[torch.Tensor]  # u8[Q]    that row holds the entry's sid
+    table: Optional[SourceTable]     # store / namespaced: the consensus table over the entry index
+    scope: Optional[torch.Tensor]    # u8[Q]    NS_* codes (store: NS_MARKET or NS_COLD)
+    rel: Optional[torch.Tensor]      # raw: the start state in batch.settle's table layout
+    conf: Optional[torch.Tensor]
+    t_us: Optional[torch.Tensor]
+    present: Optional[torch.Tensor]
+
+
+_PAIR_MODES = {"store": N.PAIR_STORE, "namespaced": N.PAIR_NAMESPACED, "raw": N.PAIR_RAW}
+
+
+def pair_resolve(qoffsets: torch.Tensor, qsid: torch.Tensor, pairs: PairTable, now_us: int, *,
+                 mode: str = "store", emarket: Optional[torch.Tensor] = None,
+                 domain: Optional[ScopeTable] = None, global_scope: Optional[ScopeTable] = None,
+                 apply_decay: bool = True, mark_cold: bool = False, index: bool = True,
+                 half_life_days: float = DECAY_HALF_LIFE_DAYS, min_rel: float = DECAY_MINIMUM) -> PairResolveResult:
+    """The market-scope row of every query entry in one launch (bce_pair_resolve).  The queries
+    are CSR by market like the table: ``qoffsets`` int64[M+1], ``qsid`` int32[Q] ascending and
+    unique inside a market (a :class:`PairPlan`'s or :class:`ReestimateCsrPlan`'s ``uoffsets`` /
+    ``usid``), ``emarket`` the market of every entry (optional: searched in ``qoffsets``).
+
+    ``mode="store"``: SQLiteReliabilityStore.get_reliability(sid, market, apply_decay) per entry;
+    ``"namespaced"``: NamespacedReliabilityStore.get_reliability with the fallback pair row ->
+    ``domain`` -> ``global_scope`` -> cold start (dense :class:`ScopeTable` over the source ranks,
+    None = not requested); ``"raw"``: the undecayed row, or the cold defaults, as the table
+    :func:`settle` updates.  ``index=False`` skips the ``lb`` / ``matched`` outputs."""
+    L = N.require_gpu()
+    md = _PAIR_MODES[mode]
+    M, Q, S = pairs.n_markets, qsid.numel(), pairs.n_sources
+    if qoffsets.numel() != M + 1:
+        raise ValueError(f"qoffsets must have n_markets + 1 = {M + 1} entries")
+    if emarket is not None and emarket.numel() != Q:
+        raise ValueError("emarket and qsid differ in length")
+    if md != N.PAIR_NAMESPACED and (domain is not None or global_scope is not None):
+        raise ValueError("domain / global_scope need mode='namespaced'")
+    dev = qoffsets.device
+    assert qoffsets.dtype == torch.int64 and qsid.dtype == torch.int32, "qoffsets int64, qsid int32"
+    assert emarket is None or emarket.dtype == torch.int32, "emarket must be int32"
+    Q1 = max(Q, 1)
+    lb = torch.empty(Q1, dtype=torch.int64, device=dev) if index else None
+    matched = torch.empty(Q1, dtype=torch.uint8, device=dev) if index else None
+    relconf = bits = scope = rel = conf = t_us = present = None
+    if md == N.PAIR_RAW:
+        rel = torch.empty(Q1, dtype=torch.float64, device=dev)
+        conf = torch.empty(Q1, dtype=torch.float64, device=dev)
+        t_us = torch.empty(Q1, dtype=torch.int64, device=dev)
+        present = torch.empty(Q1, dtype=torch.uint8, device=dev)
+    else:
+        relconf = torch.empty((Q1, 2), dtype=torch.float64, device=dev)
+        bits = torch.zeros(max((Q + 31) // 32, 1), dtype=torch.int32, device=dev)
+        scope = torch.empty(Q1, dtype=torch.uint8, device=dev)
+    dense, keep = [], []
+    for x in (domain, global_scope):
+        if x is None:
+            dense += [None] * 4
+        else:
+            assert x.rel.numel() == S and x.conf.numel() == S and x.has.numel() == S and x.t_us.numel() == S, \
+                "a dense scope must have n_sources rows"
+            arrs = (x.rel.to(torch.float64).contiguous(), x.conf.to(torch.float64).contiguous(),
+                    x.t_us.to(torch.int64).contiguous(), x.has.to(torch.uint8).contiguous())
+            keep.append(arrs)  # alive until the launch is enqueued
+            dense += [N.ptr(a) for a in arrs]
+    P = pairs.n_rows
+    tab = [N.ptr(t if P else None) for t in (pairs.psid, pairs.rel, pairs.conf, pairs.t_us, pairs.has)]
+    N.check(L.bce_pair_resolve(md, N.ptr(qoffsets), M, N.ptr(qsid if Q else None), N.ptr(emarket if Q else None), Q,
+                               N.ptr(pairs.poffsets), *tab, P, S, *dense, int(bool(apply_decay)), int(now_us),
+                               float(half_life_days), float(min_rel), DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE,
+                               int(bool(mark_cold)), N.ptr(lb), N.ptr(matched), N.ptr(relconf), N.ptr(bits),
+                               N.ptr(scope), N.ptr(rel), N.ptr(conf), N.ptr(t_us), N.ptr(present), N.stream(dev)),
+            "bce_pair_resolve")
+    cut = lambda t: None if t is None else t[:Q]  # noqa: E731
+    table = SourceTable(relconf, bits, range(Q)) if relconf is not None else None  # "names": the entry indices
+    return PairResolveResult(cut(lb), cut(matched), table, cut(scope), cut(rel), cut(conf), cut(t_us), cut(present))
+
+
+@dataclass
+class PairConsensusResult:
+    """:func:`consensus_pairs`: ``result`` is the :class:`ConsensusResult` of the batch, whose
+    per-unique rank field (``usid``) holds the ENTRY index (| cold << 31) -- the source of entry
+    ``e`` is ``plan.usid[e]``; inside a market entries ascend with the sid, so slot j of a market
+    is its j-th source as in :func:`consensus`.  ``scope`` / ``matched`` / ``lb`` are per entry."""
+
+    result: ConsensusResult
+    plan: PairPlan
+    scope: torch.Tensor
+    matched: torch.Tensor
+    lb: torch.Tensor
+
+
+def consensus_pairs(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, pairs: PairTable, now_us: int, *,
+                    plan: Optional[PairPlan] = None, domain: Optional[ScopeTable] = None,
+                    global_scope: Optional[ScopeTable] = None, namespaced: bool = False, apply_decay: bool = True,
+                    mark_cold: bool = False, **consensus_kwargs) -> PairConsensusResult:
+    """compute_consensus for every CSR market with the reliability of every signal read at
+    MARKET scope: one :func:`pair_resolve` launch builds the consensus table over the batch's
+    unique pairs, then :func:`consensus` runs unchanged with ``plan.esid`` as the ranks.
+    ``namespaced=False`` is what MarketStore.compute_all_consensus(store) reads
+    (get_reliability(sid, str(market.id), apply_decay=True), every source present);
+    ``namespaced=True`` adds the fallback to ``domain`` / ``global_scope`` / cold start.  A caller
+    that reruns the same CSR builds the :class:`PairPlan` once.  ``consensus_kwargs`` go to
+    :func:`consensus` (``plan=`` there is the length-bin :class:`Plan`, passed as ``bins``)."""
+    if plan is None:
+        plan = PairPlan.build(offsets, sid, prob, pairs.n_sources)
+    if plan.n_markets != pairs.n_markets or plan.n_sources != pairs.n_sources:
+        raise ValueError("the plan and the pair table describe different batches")
+    r = pair_resolve(plan.uoffsets, plan.usid, pairs, now_us, mode="namespaced" if namespaced else "store",
+                     emarket=plan.emarket, domain=domain, global_scope=global_scope, apply_decay=apply_decay,
+                     mark_cold=mark_cold)
+    if "bins" in consensus_kwargs:
+        consensus_kwargs["plan"] = consensus_kwargs.pop("bins")
+    res = consensus(offsets, plan.esid, prob.to(torch.float64), r.table, **consensus_kwargs)
+    return PairConsensusResult(res, plan, r.scope, r.matched, r.lb)
+
+
+def _pair_merge_index(lb: torch.Tensor, matched: torch.Tensor, touched: torch.Tensor, emarket: torch.Tensor,
+                      poffsets: torch.Tensor):
+    """Where the rows of a settled pair table go (torch only, any device).  ``lb`` / ``matched``
+    per entry (:func:`pair_resolve`), ``touched`` bool per entry; entries are in (market, sid)
+    order, so ``lb`` does not decrease.  Returns ``(dst_old, ins, dst_ins, upd, dst_upd,
+    new_poffsets)``: the new position of every old row, the entries to insert and their
+    positions, the entries that overwrite their matched row and those rows' new positions, and
+    the new row offsets."""
+    P = int(poffsets[-1]) if poffsets.numel() else 0
+    M = poffsets.numel() - 1
+    hit = matched.to(torch.bool)
+    ins = torch.nonzero(touched & ~hit).flatten()
+    upd = torch.nonzero(touched & hit).flatten()
+    # an old row p moves behind every inserted entry whose lower bound is <= p
+    shift = torch.cumsum(torch.bincount(lb[ins], minlength=P + 1), 0)
+    dst_old = torch.arange(P, dtype=torch.int64, device=lb.device) + shift[:P]
+    # the j-th inserted entry sits behind the lb old rows and the j inserts before it
+    dst_ins = lb[ins] + torch.arange(ins.numel(), dtype=torch.int64, device=lb.device)
+    dst_upd = dst_old[lb[upd]]
+    new_poffsets = poffsets.clone()
+    new_poffsets[1:] += torch.cumsum(torch.bincount(emarket[ins].to(torch.int64), minlength=M), 0)
+    return dst_old, ins, dst_ins, upd, dst_upd, new_poffsets
+
+
+def settle_pairs(plan: PairPlan, pairs: PairTable, offsets: torch.Tensor, prob: torch.Tensor,
+                 outcome: torch.Tensor, now_us: int, **settle_kwargs):
+    """``update_reliability(sid, correct, market_id=m)`` for every signal of every market with
+    ``outcome >= 0`` (int8[M]: -1 unresolved, 0, 1), at MARKET scope
+    (reliability_abstraction.py:211-229).  The chain of a pair is its signals in that market in
+    position order -- the order the reference's loop over ``market.signals`` reaches the row.
+
+    A :class:`SettlePlan` is compiled over the entry space (``plan.esid`` as the ranks), the start
+    states come from :func:`pair_resolve` in raw mode, :func:`settle` applies the chains in place
+    on that entry table, and the result is merged into a NEW :class:`PairTable`: touched pairs
+    with a row overwrite it, touched pairs without one are inserted in sid order, every other row
+    is carried over bit for bit; settled rows get ``t_us = now_us`` and ``has = 1``.  The merge's
+    destinations are cumulative sums and its row movement torch ``index_copy_`` (once per batch,
+    bytes-bound).  Returns ``(table, settle_plan)``; the plan's ``total`` / ``correct`` are the
+    counts per entry.  ``settle_kwargs`` go to :func:`settle` (``long_min``, ``chunk_bits``)."""
+    if plan.n_markets != pairs.n_markets or plan.n_sources != pairs.n_sources:
+        raise ValueError("the plan and the pair table describe different batches")
+    E = plan.n_entries
+    splan = SettlePlan.build(offsets, plan.esid, prob, outcome, n_sources=max(E, 1))
+    if E == 0:
+        return pairs, splan
+    r = pair_resolve(plan.uoffsets, plan.usid, pairs, now_us, mode="raw", emarket=plan.emarket)
+    settle(splan, r.rel, r.conf, r.t_us, r.present, now_us, **settle_kwargs)
+    dst_old, ins, dst_ins, upd, dst_upd, poffsets = _pair_merge_index(r.lb, r.matched, splan.total[:E] > 0,
+                                                                      plan.emarket, pairs.poffsets)
+    P2 = pairs.n_rows + ins.numel()
+    new = []
+    for old, ent in ((pairs.psid, plan.usid), (pairs.rel, r.rel), (pairs.conf, r.conf), (pairs.t_us, r.t_us),
+                     (pairs.has, r.present)):
+        out = torch.empty(P2, dtype=old.dtype, device=old.device)
+        out.index_copy_(0, dst_old, old)
+        out.index_copy_(0, dst_ins, ent[ins])
+        out.index_copy_(0, dst_upd, ent[upd])
+        new.append(out)
+    return PairTable(poffsets, *new, pairs.n_markets, pairs.n_sources), splan

@@ -150,13 +150,19 @@ class MarketStore:
             markets = [m for m in markets if m.id.matches(pattern)]
         return markets
 
-    def compute_all_consensus(self, reliability_store: Optional[SQLiteReliabilityStore] = None
-                              ) -> Dict[str, Dict[str, Any]]:
-        """Consensus for all open markets in ONE batched launch (market.py:200-221)."""
+    def compute_all_consensus(self, reliability_store: Optional[SQLiteReliabilityStore] = None, *,
+                              pair_table: bool = False) -> Dict[str, Dict[str, Any]]:
+        """Consensus for all open markets in ONE batched launch (market.py:200-221).
+
+        ``pair_table=True`` (with a store) reads the (source, market) rows through
+        ``load_pair_table`` and ``batch.consensus_pairs``: chunked SQL, a sparse table in HBM and
+        one lookup launch instead of a query per market and a host loop per pair.  Same dicts."""
         markets = self.list_markets(status=MarketStatus.OPEN)
         busy = [m for m in markets if m.signals]
         computed: Dict[str, Dict[str, Any]] = {}
-        if busy:
+        if busy and pair_table and reliability_store is not None:
+            computed = _batched_consensus_pairs(busy, reliability_store)
+        elif busy:
             computed = _batched_consensus(busy, reliability_store)
         results: Dict[str, Dict[str, Any]] = {}
         for market in markets:
@@ -230,6 +236,65 @@ def _batched_consensus(markets: List[Market], store: Optional[SQLiteReliabilityS
     out = {}
     for mpos, market in enumerate(markets):
         b, ids = per_market_ids[mpos]
+        a = offsets[mpos]
+        u = len(ids)
+        null = tot[mpos] == 0
+        sw = [{"sourceId": ids[j], "weight": float(weight[a + j]), "normalizedWeight": float(nweight[a + j])}
+              for j in range(u)]
+        out[str(market.id)] = {
+            "schemaVersion": SCHEMA_VERSION,
+            "consensus": None if null else float(cons[mpos]),
+            "confidence": 0.0 if null else float(confd[mpos]),
+            "sourceWeights": sw,
+            "normalization": {"totalWeight": float(tot[mpos]), "sourceCount": u},
+            "diagnostics": {
+                "status": "computed",
+                "sources": len(market.signals),
+                "uniqueSources": u,
+                "coldStartSources": [ids[j] for j in range(u) if usid[a + j] < 0],
+            },
+            "marketId": str(market.id),
+        }
+    return out
+
+
+def _batched_consensus_pairs(markets: List[Market], store: SQLiteReliabilityStore) -> Dict[str, Dict[str, Any]]:
+    """_batched_consensus with a store, through the pair table: sources ranked once over the
+    batch, the (source, market) rows loaded by ``load_pair_table`` and looked up on the GPU
+    (``batch.consensus_pairs``, store mode: every sourceId is in the dict, market.py:209-219)."""
+    rank = batch.intern(s["sourceId"] for m in markets for s in m.signals)
+    names = list(rank)
+    offsets = [0]
+    sid_list: List[int] = []
+    prob_list: List[float] = []
+    for market in markets:
+        for s in market.signals:
+            sid_list.append(rank[s["sourceId"]])
+            p = s["probability"]
+            if not isinstance(p, (int, float)):
+                0 + p  # noqa: B018  -- builtin sum()'s TypeError (core.py:116)
+            prob_list.append(float(p))
+        offsets.append(len(sid_list))
+    N.require_gpu()
+    dev = N.device()
+    T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+    pairs = store.load_pair_table([str(m.id) for m in markets], names, device=dev)
+    # get_reliability(apply_decay=True) for every pair, "now" read like decay.py:136-137
+    now_us = dt_to_us(_decay.datetime.now(timezone.utc))
+    pc = batch.consensus_pairs(T(np.array(offsets, np.int64)), T(np.array(sid_list, np.int32)),
+                               T(np.array(prob_list, np.float64)), pairs, now_us, validate=False, check=True)
+    res = pc.result
+    cons = res.consensus.cpu().numpy()
+    confd = res.confidence.cpu().numpy()
+    tot = res.total_weight.cpu().numpy()
+    usid = res.usid.cpu().numpy()
+    weight = res.weight.cpu().numpy()
+    nweight = res.nweight.cpu().numpy()
+    uoff = pc.plan.uoffsets.cpu().numpy()
+    esrc = pc.plan.usid.cpu().numpy()
+    out = {}
+    for mpos, market in enumerate(markets):
+        ids = [names[s] for s in esrc[uoff[mpos]:uoff[mpos + 1]]]  # sorted(): entries ascend with the rank
         a = offsets[mpos]
         u = len(ids)
         null = tot[mpos] == 0
@@ -375,18 +440,24 @@ class CrossMarketAggregator:
         return results
 
     def settle_resolved(self, store, domain: Optional[str] = None, update_global: bool = False,
-                        patterns: Optional[List[str]] = None, dry_run: bool = False):
+                        patterns: Optional[List[str]] = None, dry_run: bool = False, market_scope: bool = False):
         """Commit every RESOLVED market with an outcome to the reliability store: the markets
         summarize_sources counts over, in the same order (list_markets, the pattern filter, then
         ``outcome is not None``), passed as ``(signals, outcome)`` to
         ``store.settle_markets`` (:class:`NamespacedReliabilityStore`), which applies
         ``update_reliability`` per signal at the domain or global scope in one compiled batch.
-        Market-level scope is not offered: its rows are keyed by (source, market).  Returns the
-        store's summary: the records and the ``total`` / ``correct`` counts per source."""
+        ``market_scope=True`` passes ``str(market.id)`` for every resolved market, so the rows
+        keyed by (source, market) are settled instead (``update_reliability(market_id=...)``, what
+        the reference's ``report-outcome --market-id`` writes).  Returns the store's summary: the
+        records and the ``total`` / ``correct`` counts per source (per pair at market scope)."""
         markets = self._store.list_markets(status=MarketStatus.RESOLVED)
         if patterns:
             markets = [m for m in markets if any(m.id.matches(p) for p in patterns)]
         markets = [m for m in markets if m.outcome is not None]
+        if market_scope:
+            return store.settle_markets([(m.signals, m.outcome) for m in markets], domain=domain,
+                                        update_global=update_global, dry_run=dry_run,
+                                        market_ids=[str(m.id) for m in markets])
         return store.settle_markets([(m.signals, m.outcome) for m in markets], domain=domain,
                                     update_global=update_global, dry_run=dry_run)
 

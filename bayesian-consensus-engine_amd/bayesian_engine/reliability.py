@@ -18,7 +18,10 @@ Bulk paths for millions of sources:
 * :meth:`SQLiteReliabilityStore.apply_outcomes` -- one outcome per source: one GPU launch,
   then one ``executemany`` upsert in a single transaction (``dry_run`` = no write-back);
 * :meth:`SQLiteReliabilityStore.settle` -- any number of outcomes per source: a compiled batch
-  of resolved markets (``batch.SettlePlan``) applied to one domain or global scope.
+  of resolved markets (``batch.SettlePlan``) applied to one domain or global scope;
+* :meth:`SQLiteReliabilityStore.load_pair_table` / :meth:`SQLiteReliabilityStore.settle_pairs` --
+  the market-scope rows of a batch of markets as a sparse HBM table (``batch.PairTable``), and
+  the same settlement at market scope, where every (source, market) pair has a row of its own.
 """
 from __future__ import annotations
 
@@ -228,9 +231,9 @@ class SQLiteReliabilityStore:
         (:class:`batch.SettlePlan` over the rank space ``names``), any number of outcomes per
         source, in the reference's loop order: one load_table, the chain kernels, then one
         ``executemany`` upsert of the touched rows in a single transaction.  ``market_id`` is a
-        domain (``__domain__:<d>``) or the global scope key; market-level rows are keyed by
-        (source, market) and are not what a plan over many markets describes.  Returns the
-        touched sources' records."""
+        domain (``__domain__:<d>``) or the global scope key; market-level rows, keyed by
+        (source, market), are settled by :meth:`settle_pairs`.  Returns the touched sources'
+        records."""
         names = list(names)
         if len(names) != plan.n_sources:
             raise ValueError(f"the plan ranks {plan.n_sources} sources, names has {len(names)}")
@@ -249,6 +252,84 @@ class SQLiteReliabilityStore:
                 self._conn.execute("BEGIN")
                 self._conn.executemany(_UPSERT_SQL, [(r.source_id, market_id, r.reliability, r.confidence, stamp)
                                                      for r in out.values()])
+        return out
+
+    _IN_CHUNK = 900  # host parameters per statement (SQLite's default limit is 999)
+
+    def load_pair_table(self, market_ids: Sequence[str], names: Sequence[str], device=None) -> batch.PairTable:
+        """The market-scope rows of ``market_ids`` as a :class:`batch.PairTable`: row i of the
+        batch is ``market_ids[i]`` (distinct, else ``ValueError``), sources are ranked by ``names``
+        (sorted) and rows of other sources are dropped.  ``market_id IN (...)`` in chunks, never
+        one statement per market.  ``device="cpu"`` needs no GPU."""
+        market_ids = [str(m) for m in market_ids]
+        mrank = {m: i for i, m in enumerate(market_ids)}
+        if len(mrank) != len(market_ids):
+            raise ValueError("duplicate market id in market_ids")
+        srank = {n: i for i, n in enumerate(names)}
+        mk: List[int] = []
+        sd: List[int] = []
+        rel: List[float] = []
+        conf: List[float] = []
+        stamps: List[str] = []
+        for k in range(0, len(market_ids), self._IN_CHUNK):
+            chunk = market_ids[k:k + self._IN_CHUNK]
+            q = ("SELECT source_id, market_id, reliability, confidence, updated_at FROM sources "
+                 f"WHERE market_id IN ({','.join('?' * len(chunk))})")
+            for sid, mid, r, c, ts in self._conn.execute(q, chunk):
+                s = srank.get(sid)
+                if s is None:
+                    continue
+                mk.append(mrank[mid])
+                sd.append(s)
+                rel.append(r)
+                conf.append(c)
+                stamps.append(ts)
+        dev = device if device is not None else N.device()
+        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        has = np.fromiter((1 if ts else 0 for ts in stamps), np.uint8, len(stamps))
+        return batch.PairTable.from_rows(T(np.asarray(mk, np.int64)), T(np.asarray(sd, np.int32)),
+                                         T(np.asarray(rel, np.float64)), T(np.asarray(conf, np.float64)),
+                                         T(iso_to_us_many(stamps)), T(has), len(market_ids), max(len(srank), 1))
+
+    def settle_pairs(self, market_ids: Sequence[str], names: Sequence[str], offsets, sid, prob, outcome,
+                     dry_run: bool = False, now: Optional[datetime] = None) -> Dict[tuple, ReliabilityRecord]:
+        """``update_reliability(source, market_id, correct)`` for every signal of every market of
+        the CSR batch with ``outcome >= 0``, at MARKET scope, in the reference's loop order:
+        :meth:`load_pair_table`, :func:`batch.settle_pairs`, then one ``executemany`` upsert of the
+        touched pairs in a single transaction (``dry_run``: no write).  ``offsets`` / ``sid`` /
+        ``prob`` / ``outcome`` are arrays or tensors; market i is ``market_ids[i]``, ranks index
+        ``names``.  Returns ``{(source_id, market_id): record}`` of the touched pairs."""
+        N.require_gpu()
+        dev = N.device()
+        market_ids = [str(m) for m in market_ids]
+        names = list(names)
+        T = lambda a, dt: torch.as_tensor(np.asarray(a) if not isinstance(a, torch.Tensor) else a).to(dev, dt)  # noqa: E731
+        offsets, sid = T(offsets, torch.int64), T(sid, torch.int32)
+        prob, outcome = T(prob, torch.float64), T(outcome, torch.int8)
+        if offsets.numel() != len(market_ids) + 1:
+            raise ValueError("offsets must have len(market_ids) + 1 entries")
+        pairs = self.load_pair_table(market_ids, names, device=dev)
+        plan = batch.PairPlan.build(offsets, sid, prob, pairs.n_sources)
+        now_us = dt_to_us(now or datetime.now(timezone.utc))
+        settled, splan = batch.settle_pairs(plan, pairs, offsets, prob, outcome, now_us)
+        E = plan.n_entries
+        # every touched pair now has a row: read them back per entry
+        r = batch.pair_resolve(plan.uoffsets, plan.usid, settled, now_us, mode="raw", emarket=plan.emarket)
+        touched = torch.nonzero(splan.total[:E] > 0).flatten()
+        em = plan.emarket[touched].cpu().numpy()
+        us = plan.usid[touched].cpu().numpy()
+        rel = r.rel[touched].cpu().numpy()
+        conf = r.conf[touched].cpu().numpy()
+        N.check_faults(dev, "settle_pairs")
+        stamp = us_to_iso(now_us)
+        out = {(names[int(s)], market_ids[int(m)]): ReliabilityRecord(names[int(s)], market_ids[int(m)], float(x),
+                                                                      float(c), stamp)
+               for m, s, x, c in zip(em, us, rel, conf)}
+        if not dry_run and out:
+            with self._conn:  # one transaction
+                self._conn.execute("BEGIN")
+                self._conn.executemany(_UPSERT_SQL, [(r_.source_id, r_.market_id, r_.reliability, r_.confidence,
+                                                      stamp) for r_ in out.values()])
         return out
 
     def fetch_pairs(self, pairs: Sequence[tuple]) -> Dict[tuple, tuple]:

@@ -205,7 +205,8 @@ class NamespacedReliabilityStore:
         return table, scope, chosen
 
     def settle_markets(self, markets: Sequence[tuple], domain: Optional[str] = None, update_global: bool = False,
-                       dry_run: bool = False, now: Optional[datetime] = None) -> "SettleSummary":
+                       dry_run: bool = False, now: Optional[datetime] = None,
+                       market_ids: Optional[Sequence[str]] = None) -> "SettleSummary":
         """``update_reliability(sid, correct, domain=domain, update_global=update_global)`` for
         every signal of every resolved market, in list order, as ONE compiled batch.
 
@@ -215,11 +216,24 @@ class NamespacedReliabilityStore:
         interned in sorted() order, one :class:`batch.SettlePlan` is built and applied to the
         ``__domain__:<domain>`` scope, or to ``__global__`` when ``domain`` is None; with
         ``update_global`` and a domain the same plan is applied a second time to ``__global__``
-        (reliability_abstraction.py:225-229).  Market-level scope is out of scope here: there the
-        rows are keyed by (source, market), every market has rows of its own and a chain is only
-        a market's duplicate signals -- use update_reliability(market_id=...).  ``dry_run``
-        computes the records and writes nothing."""
+        (reliability_abstraction.py:225-229).  ``dry_run`` computes the records and writes nothing.
+
+        ``market_ids`` (one truthy, distinct id per entry of ``markets``, else ``ValueError``)
+        settles at MARKET scope instead, as ``update_reliability(sid, correct, market_id=m, ...)``
+        chooses it (:211-216; ``domain`` is ignored there, as in the reference): every (source,
+        market) pair has a row of its own and its chain is that market's signals of the source
+        (:meth:`SQLiteReliabilityStore.settle_pairs`).  The summary's ``records`` / ``total`` /
+        ``correct`` are then keyed by ``(source_id, market_id)``; with ``update_global`` the
+        source-scope plan also settles ``__global__``."""
         markets = [(list(signals), outcome) for signals, outcome in markets]
+        if market_ids is not None:
+            market_ids = list(market_ids)
+            if len(market_ids) != len(markets):
+                raise ValueError(f"market_ids has {len(market_ids)} entries for {len(markets)} markets")
+            if not all(market_ids):
+                raise ValueError("every market id must be truthy (a falsy one selects another scope)")
+            if len(set(market_ids)) != len(market_ids):
+                raise ValueError("duplicate market id in market_ids")
         rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
         names = list(rank)
         offsets = [0]
@@ -248,6 +262,29 @@ class NamespacedReliabilityStore:
                                       T(np.array(prob_list, np.float64)), T(np.array(outcome_list, np.int8)),
                                       len(names))
         now = now or datetime.now(timezone.utc)
+        if market_ids is not None:
+            mids = [str(m) for m in market_ids]
+            precs = self._store.settle_pairs(mids, names, np.array(offsets, np.int64), np.array(sid_list, np.int32),
+                                             np.array(prob_list, np.float64), np.array(outcome_list, np.int8),
+                                             dry_run=dry_run, now=now)
+            records = {k: NamespacedReliabilityRecord(k[0], ReliabilityNamespace.MARKET, k[1], r.reliability,
+                                                      r.confidence, r.updated_at, False) for k, r in precs.items()}
+            global_records = {}
+            if update_global:
+                grecs = self._store.settle(self.GLOBAL_MARKET_ID, names, plan, dry_run=dry_run, now=now)
+                global_records = {sid: NamespacedReliabilityRecord(sid, ReliabilityNamespace.GLOBAL, "global",
+                                                                   r.reliability, r.confidence, r.updated_at, False)
+                                  for sid, r in grecs.items()}
+            ptotal = dict.fromkeys(records, 0)
+            pcorrect = dict.fromkeys(records, 0)
+            for mid, (signals, outcome) in zip(mids, markets):
+                if outcome is None:
+                    continue
+                for s in signals:
+                    k = (s["sourceId"], mid)
+                    ptotal[k] += 1
+                    pcorrect[k] += int((s.get("probability", 0.5) >= 0.5) == bool(outcome))
+            return SettleSummary(records, global_records, ptotal, pcorrect)
         recs = self._store.settle(target, names, plan, dry_run=dry_run, now=now)
         records = {sid: NamespacedReliabilityRecord(sid, namespace, value, r.reliability, r.confidence,
                                                     r.updated_at, False) for sid, r in recs.items()}

@@ -9,32 +9,13 @@
 // and written with 16-byte accesses.  FP contraction off (CPython rounding).
 #include "bce_device.hpp"
 #include "bce_internal.hpp"
+#include "decay_device.hpp"  // DecayConst, decayed(), NsScope
 #include "glibc_pow.hpp"
 #include "reliability_update.hpp"
 
 #pragma clang fp contract(off)
 
 namespace bce {
-
-struct DecayConst {
-  int64_t now_us;
-  double half_life;
-  double min_rel;
-  double default_rel;
-  double default_conf;
-};
-
-// decay.py:52-58 and 90-100, with days from decay.py:140-145.
-__device__ __forceinline__ double decayed(double r, int64_t t_us, const DecayConst& k,
-                                          const unsigned long long* tab = kExpTab) {
-  if (t_us == BCE_NO_TIMESTAMP) return r;
-  const double secs = (double)(k.now_us - t_us) / 1e6;  // timedelta.total_seconds()
-  const double days = py_max(0.0, secs / 86400.0);
-  if (!(days > 0.0)) return r;
-  const double f = bce_pow::pow_base2(-days / k.half_life, tab);  // 2.0 ** x as libm pow (glibc_pow.hpp)
-  const double d = k.min_rel + (r - k.min_rel) * f;
-  return py_max(k.min_rel, py_min(1.0, d));
-}
 
 // update_one (reliability.py:163-173 for one participant) lives in reliability_update.hpp.
 
@@ -188,12 +169,6 @@ __global__ __launch_bounds__(256) void replay_step_kernel(int64_t n, double* __r
 // has a truthy updated_at supplies the record -- decayed as
 // SQLiteReliabilityStore.get_reliability does (reliability.py:110-131) -- else the
 // cold-start defaults (:177-186).  One pass writes the packed consensus table directly.
-struct NsScope {
-  const double* rel;
-  const double* conf;
-  const int64_t* t_us;
-  const uint8_t* has;
-};
 struct NsArgs {
   NsScope sc[3];
   int n_scopes;  // leading non-NULL scopes after compaction (host)

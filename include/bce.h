@@ -420,6 +420,54 @@ int bce_settle_apply(const uint64_t* bits, int64_t n_bits, const int64_t* start,
                      uint8_t* present, int64_t now_us, double default_rel, double default_conf, double* snap,
                      void* stream);
 
+/* ---- market-scope rows: the (source, market) rows of the store, looked up per pair ----------
+ * Replaces, for every unique (market, source) pair of a batch, one call of
+ *   BCE_PAIR_STORE       SQLiteReliabilityStore.get_reliability(sid, market_id, apply_decay)
+ *                        (reliability.py:104-140) -- what MarketStore.compute_all_consensus reads
+ *                        per signal (market.py:200-221);
+ *   BCE_PAIR_NAMESPACED  NamespacedReliabilityStore.get_reliability(sid, market_id, domain,
+ *                        apply_decay) (reliability_abstraction.py:137-188);
+ *   BCE_PAIR_RAW         the undecayed row compute_update starts from (reliability.py:161), as
+ *                        update_reliability(sid, correct, market_id=m) reads it
+ *                        (reliability_abstraction.py:211-229).
+ * The table is CSR by market over the batch's market index: poffsets[n_markets + 1], psid[n_rows]
+ * (source ranks, strictly ascending inside a market), prel / pconf / pt_us (BCE_NO_TIMESTAMP =
+ * falsy or unparseable updated_at) / phas (updated_at is truthy).  The queries have the same
+ * layout: qoffsets[n_markets + 1], qsid[n_queries] ascending and unique inside a market (the
+ * uoffsets / usid of bce_reestimate_csr_compile); emarket[n_queries] (nullable) = the market of
+ * every entry, else it is searched in qoffsets.  Per entry e the kernel writes lb[e] = the lower
+ * bound of qsid[e] in its market's rows (a global row index in [poffsets[m], poffsets[m + 1]]) and
+ * matched[e] = that row holds the same sid; then
+ *   STORE: a row that exists supplies (rel, conf) whatever its has, rel decayed at now_us when
+ *     apply_decay and t_us != BCE_NO_TIMESTAMP; no row = (default_rel, default_conf).  scope[e] =
+ *     0 for a row, 3 for the cold start;
+ *   NAMESPACED: the pair's row where has, else the dense domain row drel.. [n_sources] where has,
+ *     else the dense global row grel.., else the cold start; each decayed by its own t_us; a NULL
+ *     drel / grel skips the scope (a falsy domain, :150).  scope[e] = 0 / 1 / 2 / 3;
+ *   both write relconf[2 * n_queries] (the packed consensus table over the ENTRY index, 16-byte
+ *     aligned) and present_bits[ceil(n_queries / 32)] (every entry, or with mark_cold only the
+ *     entries that resolved to a stored row);
+ *   RAW: out_rel / out_conf / out_t_us / out_present [n_queries] = the row, or the defaults,
+ *     BCE_NO_TIMESTAMP and 0: the table layout of bce_settle_apply over the entry index.
+ * Every output is nullable.  A qsid outside [0, n_sources) is clamped and raises the device fault
+ * word; so do offsets that decrease or leave [0, n_queries] / [0, n_rows] (such a market's rows
+ * are searched as an empty segment) (bce_fault_check). */
+enum bce_pair_mode {
+    BCE_PAIR_STORE = 0,
+    BCE_PAIR_NAMESPACED = 1,
+    BCE_PAIR_RAW = 2
+};
+int bce_pair_resolve(int32_t mode, const int64_t* qoffsets, int64_t n_markets, const int32_t* qsid,
+                     const int32_t* emarket, int64_t n_queries, const int64_t* poffsets, const int32_t* psid,
+                     const double* prel, const double* pconf, const int64_t* pt_us, const uint8_t* phas,
+                     int64_t n_rows, int32_t n_sources, const double* drel, const double* dconf,
+                     const int64_t* dt_us, const uint8_t* dhas, const double* grel, const double* gconf,
+                     const int64_t* gt_us, const uint8_t* ghas, int apply_decay, int64_t now_us,
+                     double half_life_days, double min_rel, double default_rel, double default_conf,
+                     int mark_cold, int64_t* lb, uint8_t* matched, double* relconf, uint32_t* present_bits,
+                     uint8_t* scope, double* out_rel, double* out_conf, int64_t* out_t_us, uint8_t* out_present,
+                     void* stream);
+
 /* ---- JSONL front end (host C++, no GPU): SURVEY §8 f2 -----------------------------------
  *
  * Replaces, for a batch: cli._cmd_consensus_legacy / _cmd_consensus (cli.py:25-52,163-174)
