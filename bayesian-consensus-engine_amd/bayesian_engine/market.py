@@ -41,6 +41,14 @@ from .timeutil import NO_TIMESTAMP, dt_to_us, iso_to_us
 
 __all__ = ["MarketId", "MarketStatus", "Market", "MarketStore", "SourcePerformance", "CrossMarketAggregator"]
 
+# device_match=None: (markets) x (patterns) from which the pattern filters take the GPU route when
+# a GPU is visible.  Measured crossover (tools/bench_glob.py part (e), name table cached): the
+# device route is clear of the fnmatch loop in every repetition from 1792 pairs up (0.77 against
+# 1.16 ms) and behind it at 448 (0.73 against 0.49 ms); rounded up to a power of two.  None = never.
+DEVICE_MATCH_MIN_PAIRS: Optional[int] = 2048
+# aggregate_many's device route: bytes of match bitmap held at once (more patterns: several runs)
+GLOB_BITMAP_BUDGET = 4 << 30
+
 
 @dataclass(frozen=True)
 class MarketId:
@@ -119,6 +127,7 @@ class MarketStore:
 
     def __init__(self):
         self._markets: Dict[str, Market] = {}
+        self._names: Optional[batch.NameTable] = None  # the ids in list_markets order, in HBM
 
     def create_market(self, market_id: MarketId, metadata: Optional[Dict[str, Any]] = None) -> Market:
         key = str(market_id)
@@ -126,6 +135,7 @@ class MarketStore:
             raise ValueError(f"Market {market_id} already exists")
         market = Market(id=market_id, metadata=metadata or {})
         self._markets[key] = market
+        self._names = None
         return market
 
     def get_market(self, market_id: MarketId) -> Optional[Market]:
@@ -149,6 +159,27 @@ class MarketStore:
         if pattern is not None:
             markets = [m for m in markets if m.id.matches(pattern)]
         return markets
+
+    def name_table(self) -> "batch.NameTable":
+        """The ids of every market in ``list_markets()`` order, packed in HBM for the glob kernel;
+        cached, rebuilt after a market is created."""
+        N.require_gpu()
+        if self._names is None or self._names.n != len(self._markets):
+            self._names = batch.NameTable.from_strings(list(self._markets), N.device())
+        return self._names
+
+    def match_many(self, patterns: List[str]):
+        """Every pattern against every market id in one launch (``batch.glob_match``):
+        ``(globs, bits)``.  Row ``globs.index[i]`` of ``bits`` holds, at the market's position in
+        ``list_markets()``, whether ``market.id.matches(patterns[i])`` (market.py:74-82)."""
+        globs = batch.GlobSet.compile(patterns)
+        return globs, batch.glob_match(self.name_table(), globs)
+
+    def match_any(self, patterns: List[str]) -> np.ndarray:
+        """bool [n_markets] in ``list_markets()`` order: the id matches any of the patterns."""
+        globs, bits = self.match_many(patterns)
+        rows = torch.tensor(sorted(set(globs.index)), dtype=torch.int64, device=bits.device)
+        return batch.glob_mask(batch.glob_any(bits, rows), len(self._markets)).cpu().numpy()
 
     def compute_all_consensus(self, reliability_store: Optional[SQLiteReliabilityStore] = None, *,
                               pair_table: bool = False) -> Dict[str, Dict[str, Any]]:
@@ -342,10 +373,36 @@ class CrossMarketAggregator:
     def __init__(self, market_store: MarketStore):
         self._store = market_store
 
-    def summarize_sources(self, patterns: Optional[List[str]] = None) -> Dict[str, SourcePerformance]:
-        markets = self._store.list_markets(status=MarketStatus.RESOLVED)
-        if patterns:
-            markets = [m for m in markets if any(m.id.matches(p) for p in patterns)]
+    def _device_route(self, n_patterns: int, device_match: Optional[bool]) -> bool:
+        """``device_match``: True / False force the GPU glob kernels / the fnmatch loop; None picks
+        the GPU once (markets) x (patterns) reaches DEVICE_MATCH_MIN_PAIRS.  Without a visible GPU
+        None keeps the fnmatch loop, so the calls that never reach a kernel (nothing matched, a
+        store of one's own behind settle_resolved) still need none; True raises NativeUnavailable."""
+        if device_match is not None:
+            return bool(device_match)
+        if DEVICE_MATCH_MIN_PAIRS is None or not torch.cuda.is_available():
+            return False
+        return len(self._store._markets) * n_patterns >= DEVICE_MATCH_MIN_PAIRS
+
+    def _select(self, status: Optional[MarketStatus], patterns: Optional[List[str]],
+                device_match: Optional[bool], with_signals: bool = False) -> List[Market]:
+        """list_markets(status), optionally only markets with signals, filtered by "matches any
+        pattern", order kept; on the device route the pattern filter is one launch over every id
+        (MarketStore.match_any)."""
+        if not patterns or not self._device_route(len(patterns), device_match):
+            markets = self._store.list_markets(status=status)
+            if with_signals:
+                markets = [m for m in markets if m.signals]
+            if patterns:
+                markets = [m for m in markets if any(m.id.matches(p) for p in patterns)]
+            return markets
+        hit = self._store.match_any(patterns)
+        return [m for m, h in zip(self._store.list_markets(), hit)
+                if h and (status is None or m.status == status) and (m.signals or not with_signals)]
+
+    def summarize_sources(self, patterns: Optional[List[str]] = None,
+                          device_match: Optional[bool] = None) -> Dict[str, SourcePerformance]:
+        markets = self._select(MarketStatus.RESOLVED, patterns, device_match)
         markets = [m for m in markets if m.outcome is not None]
         order: Dict[str, int] = {}
         names: List[str] = []
@@ -387,7 +444,7 @@ class CrossMarketAggregator:
         return results
 
     def reestimate_sources(self, iters: int = 10, patterns: Optional[List[str]] = None,
-                           prior: float = 0.5) -> Dict[str, SourcePerformance]:
+                           prior: float = 0.5, device_match: Optional[bool] = None) -> Dict[str, SourcePerformance]:
         """Learned source reliabilities over every market that has signals, resolved or not:
         ``iters`` rounds of consensus <-> reliability (batch.reestimate_csr), every source
         starting at ``prior``.  A RESOLVED market with an outcome is scored against that outcome,
@@ -397,9 +454,7 @@ class CrossMarketAggregator:
         consensus sums in compute_consensus's order (core.py:103).  ``reliability`` is the
         weight after the last round; the counts and market lists are the last round's, laid
         out as summarize_sources lays them out."""
-        markets = [m for m in self._store.list_markets() if m.signals]
-        if patterns:
-            markets = [m for m in markets if any(m.id.matches(p) for p in patterns)]
+        markets = self._select(None, patterns, device_match, with_signals=True)
         results: Dict[str, SourcePerformance] = {}
         if not markets:
             return results
@@ -440,7 +495,8 @@ class CrossMarketAggregator:
         return results
 
     def settle_resolved(self, store, domain: Optional[str] = None, update_global: bool = False,
-                        patterns: Optional[List[str]] = None, dry_run: bool = False, market_scope: bool = False):
+                        patterns: Optional[List[str]] = None, dry_run: bool = False, market_scope: bool = False,
+                        device_match: Optional[bool] = None):
         """Commit every RESOLVED market with an outcome to the reliability store: the markets
         summarize_sources counts over, in the same order (list_markets, the pattern filter, then
         ``outcome is not None``), passed as ``(signals, outcome)`` to
@@ -450,9 +506,7 @@ class CrossMarketAggregator:
         keyed by (source, market) are settled instead (``update_reliability(market_id=...)``, what
         the reference's ``report-outcome --market-id`` writes).  Returns the store's summary: the
         records and the ``total`` / ``correct`` counts per source (per pair at market scope)."""
-        markets = self._store.list_markets(status=MarketStatus.RESOLVED)
-        if patterns:
-            markets = [m for m in markets if any(m.id.matches(p) for p in patterns)]
+        markets = self._select(MarketStatus.RESOLVED, patterns, device_match)
         markets = [m for m in markets if m.outcome is not None]
         if market_scope:
             return store.settle_markets([(m.signals, m.outcome) for m in markets], domain=domain,
@@ -472,10 +526,18 @@ class CrossMarketAggregator:
         """Cross-market aggregation (market.py:338-408), computed by bce_aggregate_groups."""
         return self.aggregate_many([patterns], method)[0]
 
-    def aggregate_many(self, pattern_lists: List[List[str]], method: str = "weighted_average") -> List[Dict[str, Any]]:
+    def aggregate_many(self, pattern_lists: List[List[str]], method: str = "weighted_average",
+                       device_match: Optional[bool] = None) -> List[Dict[str, Any]]:
         """aggregate_consensus for many pattern lists in ONE kernel launch: each list is a
         member group (markets in list_markets order per pattern, duplicates kept,
-        market.py:355-357); the sums run in that order on the GPU (bit-exact)."""
+        market.py:355-357); the sums run in that order on the GPU (bit-exact).
+
+        ``device_match`` (see ``_device_route``): the member groups come from the glob kernels
+        (``MarketStore.match_many`` + ``batch.glob_members``) instead of one fnmatch call per
+        (pattern, market) pair; same dicts."""
+        n_patterns = sum(len(patterns) for patterns in pattern_lists)
+        if n_patterns and self._device_route(n_patterns, device_match):
+            return self._aggregate_many_device(pattern_lists, method)
         groups: List[List[int]] = []
         index: Dict[str, int] = {}
         cons: List[float] = []
@@ -519,6 +581,70 @@ class CrossMarketAggregator:
                 out.append(dict(empty, marketsIncluded=0))
             elif k[gi] == 0:
                 out.append(dict(empty, marketsIncluded=len(g)))
+            else:
+                out.append({"schemaVersion": "1.0.0", "consensus": float(pick[gi]), "confidence": float(mconf[gi]),
+                            "marketsIncluded": int(k[gi]), "method": method})
+        return out
+
+    def _aggregate_many_device(self, pattern_lists: List[List[str]], method: str) -> List[Dict[str, Any]]:
+        """aggregate_many with the member groups built in HBM: one match launch over every id,
+        count + fill into ``group_offsets`` / ``members``.  The value arrays are indexed by store
+        position (the host route indexes them in first-seen order; no output depends on it)."""
+        markets = self._store.list_markets()
+        M = len(markets)
+        # the bitmap is (patterns) x ceil(M / 64) words: pattern lists are taken in runs whose bitmap
+        # stays inside GLOB_BITMAP_BUDGET, each run matched and expanded on its own
+        per_run = max(GLOB_BITMAP_BUDGET // (8 * ((M + 63) // 64) or 1), 1)
+        runs, n = [[]], 0
+        for patterns in pattern_lists:
+            if runs[-1] and n + len(patterns) > per_run:
+                runs.append([])
+                n = 0
+            runs[-1].append(patterns)
+            n += len(patterns)
+        goffs, mems, base = [], [], 0
+        for run in runs:
+            globs, bits = self._store.match_many([p for patterns in run for p in patterns])
+            slot_groups = np.zeros(len(run) + 1, np.int64)
+            slot_groups[1:] = np.cumsum([len(patterns) for patterns in run])
+            rows = torch.tensor(globs.index, dtype=torch.int64, device=bits.device)
+            goff, mem = batch.glob_members(bits, M, rows, slot_groups)
+            goffs.append(goff[(1 if goffs else 0):] + base)
+            mems.append(mem)
+            base += mem.numel()
+            del bits
+        goff, members = torch.cat(goffs), torch.cat(mems)
+        dev = goff.device
+        sizes = np.diff(goff.cpu().numpy())
+        cons = np.zeros(max(M, 1), np.float64)
+        conf = np.zeros(max(M, 1), np.float64)
+        has = np.zeros(max(M, 1), np.uint8)
+        if members.numel():
+            # the matched markets in first-seen order: the order the host route reads their results in
+            srt, idx = torch.sort(members, stable=True)
+            head = torch.ones_like(srt, dtype=torch.bool)
+            head[1:] = srt[1:] != srt[:-1]
+            seen = srt[head][torch.argsort(idx[head])]
+            for m in seen.cpu().tolist():
+                res = markets[m].consensus_result
+                if bool(res) and res.get("consensus") is not None:  # market.py:369-370
+                    cons[m] = float(res["consensus"])
+                    conf[m] = float(res.get("confidence", 0.5))
+                    has[m] = 1
+        empty = {"schemaVersion": "1.0.0", "consensus": None, "confidence": 0.0}
+        if not has.any():
+            return [dict(empty, marketsIncluded=int(n)) for n in sizes]
+        if method not in ("weighted_average", "median", "majority"):
+            raise ValueError(f"Unknown aggregation method: {method}")  # some group has a consensus
+        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        r = batch.aggregate(goff, members, T(cons), T(conf), T(has), median=method == "median")
+        pick = {"weighted_average": r.wavg, "median": r.median, "majority": r.majority}[method].cpu().numpy()
+        mconf = r.mean_conf.cpu().numpy()
+        k = r.n_included.cpu().numpy()
+        out = []
+        for gi, n in enumerate(sizes):
+            if k[gi] == 0:
+                out.append(dict(empty, marketsIncluded=int(n)))
             else:
                 out.append({"schemaVersion": "1.0.0", "consensus": float(pick[gi]), "confidence": float(mconf[gi]),
                             "marketsIncluded": int(k[gi]), "method": method})

@@ -468,6 +468,58 @@ int bce_pair_resolve(int32_t mode, const int64_t* qoffsets, int64_t n_markets, c
                      uint8_t* scope, double* out_rel, double* out_conf, int64_t* out_t_us, uint8_t* out_present,
                      void* stream);
 
+/* ---- market-id glob patterns: MarketId.matches for every (pattern, market) pair ------
+ *
+ * Replaces, for a batch: MarketId.matches (market.py:74-82) under MarketStore.list_markets(
+ * pattern=...) (:184-198), one fnmatch call per pair, and the member loop of
+ * CrossMarketAggregator.aggregate_consensus (:352-357).  Names are the ids in list_markets order,
+ * UTF-8 ('surrogatepass': a lone surrogate is its 3-byte sequence): name m is
+ * name_bytes[name_off[m] .. name_off[m+1]).  Patterns are compiled on the host
+ * (batch.GlobSet.compile, CPython 3.10's fnmatch.translate restated) into 32-bit ops, pattern p
+ * = prog[prog_off[p] .. prog_off[p+1]), kind in bits 31..29:
+ *   0 literal   bits 20..0 = the code point
+ *   1 any one code point ('?')
+ *   2 star      any run of code points, newline included (a run of '*' is one op)
+ *   3 class     bits 27..0 = class index c, bit 28 = negate; class c is the inclusive code-point
+ *               ranges (cls_rng[2r], cls_rng[2r+1]) for r in cls_off[c] .. cls_off[c+1]; a class
+ *               without ranges never matches (negated: always)
+ * A pattern matches a name exactly when fnmatch.fnmatchcase(name, pattern) is true (csrc/
+ * glob_match.hpp: the iterative matcher, one saved position per star, decoding forward).  The
+ * compiler declines a pattern of more than BCE_GLOB_MAX_OPS ops or with a class of more than
+ * BCE_GLOB_MAX_RANGES ranges; the caller evaluates a declined pattern with fnmatch on the host and
+ * uploads its row (the kernels themselves have no such limit).
+ *
+ * bce_glob_match: bits[P][ceil(M / 64)]: bit m % 64 of word m / 64 of row p is set iff pattern p
+ *   matches name m; bits at positions >= M are zero; every word is written exactly once.  Names of
+ *   at most 64 bytes are matched from LDS, longer ones from global memory.  Names that are not
+ *   UTF-8 give unspecified bits.
+ * bce_glob_match_host: the same matcher compiled for the CPU over HOST arrays, no GPU (the
+ *   tradition of bce_debug_py_round); malformed offsets or programs return BCE_EINVAL.
+ * bce_glob_count: cnt[r] = the number of set bits of row rows[r] (a row may be listed many times).
+ * bce_glob_fill: members[slot_off[r] .. slot_off[r+1]) = the set bit positions of row rows[r],
+ *   ascending; slot_off = the exclusive cumulative sum of cnt, n_members = slot_off[R].  A group is
+ *   a run of consecutive slots, so bce_aggregate_groups' group_offsets is slot_off sampled at the
+ *   group boundaries: members per pattern in list order, inside a pattern in store order,
+ *   duplicates kept (:352-357).
+ * On the device, offsets that decrease or leave their array, an op kind or class index outside its
+ * table, a row outside [0, P) and a slot that does not hold its row's count raise the device fault
+ * word (bce_fault_check); the affected pair counts as no match, and nothing is read or written
+ * outside the arrays. */
+#define BCE_GLOB_MAX_OPS 256   /* ops of a compiled pattern */
+#define BCE_GLOB_MAX_RANGES 64 /* ranges of one bracket expression */
+int bce_glob_match(const uint8_t* name_bytes, int64_t n_bytes, const int64_t* name_off, int64_t M,
+                   const uint32_t* prog, int64_t n_ops, const int64_t* prog_off, int64_t P,
+                   const uint32_t* cls_rng, int64_t n_rng, const int32_t* cls_off, int64_t n_cls,
+                   uint64_t* bits, void* stream);
+int bce_glob_match_host(const uint8_t* name_bytes, int64_t n_bytes, const int64_t* name_off, int64_t M,
+                        const uint32_t* prog, int64_t n_ops, const int64_t* prog_off, int64_t P,
+                        const uint32_t* cls_rng, int64_t n_rng, const int32_t* cls_off, int64_t n_cls,
+                        uint64_t* bits);
+int bce_glob_count(const uint64_t* bits, int64_t M, int64_t P, const int64_t* rows, int64_t R, int64_t* cnt,
+                   void* stream);
+int bce_glob_fill(const uint64_t* bits, int64_t M, int64_t P, const int64_t* rows, int64_t R,
+                  const int64_t* slot_off, int64_t n_members, int64_t* members, void* stream);
+
 /* ---- JSONL front end (host C++, no GPU): SURVEY §8 f2 -----------------------------------
  *
  * Replaces, for a batch: cli._cmd_consensus_legacy / _cmd_consensus (cli.py:25-52,163-174)
