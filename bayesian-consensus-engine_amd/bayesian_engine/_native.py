@@ -63,6 +63,7 @@ _SIGS = {
     "bce_table_pack": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bce_validate_csr": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
     "bce_plan_bins": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    "bce_plan_schedule": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
     "bce_consensus_scratch_bytes": (C.c_int64, [_vp, _vp, _vp]),
     "bce_plan_bins_device": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "bce_plan_device_scratch_bytes": (_i64, [_i64]),

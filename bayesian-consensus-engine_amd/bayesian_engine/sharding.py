@@ -18,6 +18,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import _native
+
 
 def shard_markets(offsets_host: np.ndarray, world: int, rank: int) -> Tuple[int, int]:
     """Contiguous market range [m0, m1) of ``rank`` so every rank gets ~N/world signals."""
@@ -33,7 +35,7 @@ def shard_markets(offsets_host: np.ndarray, world: int, rank: int) -> Tuple[int,
     return int(cuts[rank]), int(cuts[rank + 1])
 
 
-# Length bins of the planned consensus launch (consensus.hip kBinMax, BCE_NBINS = 13): bins 0..3
+# Length bins of the planned consensus launch (plan_host.hpp kBinMax, BCE_NBINS = 13): bins 0..3
 # (n <= 64) run lane/segment kernels on the side stream, 4..11 the wide kernels, 12 (> 4096) the
 # long kernel.
 BIN_MAX = np.array([8, 16, 32, 64, 128, 256, 512, 1024, 1536, 2048, 3072, 4096], np.int64)
@@ -65,7 +67,7 @@ def market_bins(offsets_host: np.ndarray) -> np.ndarray:
 def plan_order(offsets_host: np.ndarray):
     """(order int32[M], bin_start int64[14]) exactly as bce_plan_bins builds them: markets grouped
     by length bin in bin order, market order inside bins 0..3 and 12, longest first (LPT, ties
-    by market order) inside the wide bins 4..11 (consensus.hip bce_plan_bins)."""
+    by market order) inside the wide bins 4..11 (plan.hip bce_plan_bins)."""
     off = np.asarray(offsets_host, np.int64)
     lens = np.diff(off)
     if len(lens) and int(lens.min()) < 0:
@@ -88,40 +90,44 @@ def _equal_cost_cut(c: np.ndarray, world: int) -> np.ndarray:
     return np.maximum.accumulate(np.clip(cuts, 0, n))
 
 
-# The launch model of bce_consensus_planned's main stream (consensus.hip), for pricing a rank's
-# wide / long markets: resident workgroups of each wide bin's kernel on one MI355X (256 CUs; the
-# grid sizes in the traces, profiles/r06k/), the merge rules (kMergeRounds = 6: FAST merges the
-# non-power-of-two bins 1025..1536 / 2049..3072 into the launch of the bin above and the 65..512
-# bins into one 1-wave launch when a launch would fill fewer than 6 resident rounds; EXACT always
-# merges the non-power-of-two bins), the cost per market of a bin's markets run on the wider
+# The launch model of bce_consensus_planned's main stream, for pricing a rank's wide / long
+# markets: resident workgroups of each wide bin's kernel on one MI355X (256 CUs; the grid sizes
+# in the traces, profiles/r06k/), which the library's own launch and merge rules
+# (bce_plan_schedule: plan_host.hpp plan_schedule, the function bce_consensus_planned launches
+# from) turn into the rank's launches; the cost per market of a bin's markets run on the wider
 # kernel of a merged launch (profiles/r06d/ pieces), and a per-launch ramp + tail.  Linear in the
 # market count: a model that charged whole rounds of resident workgroups (ceil(n / R)) balanced
 # worse (0.84 against 0.91 of linear, profiles/r06l/) -- the workgroups of a persistent launch
 # drift apart and its LPT order ends it on its cheapest markets, so partial rounds cost little.
 _RESIDENT = {4: 5120, 5: 4096, 6: 4096, 7: 2048, 8: 1280, 9: 1024, 10: 512, 11: 512}
-_MERGE_ROUNDS = 6.0
 _LAUNCH_US = 6.0
 _MERGED_COST_US = {"fast": {4: 0.0029, 5: 0.0033, 8: 0.0190, 10: 0.0416},
                    "exact": {4: 0.0031, 5: 0.0035, 8: 0.0218, 10: 0.0647}}
 
 
+def plan_schedule(bin_start: Optional[np.ndarray], mode: str, resident=_RESIDENT):
+    """The library's launches for a plan (bce_plan_schedule; no GPU needed): ``([(b0, b1, side),
+    ...] in issue order, fork)`` -- the markets of bins b0..b1 in one kernel sized for bin b1.
+    ``bin_start`` None: the device-planned launch.  ``resident``: workgroups per wide bin."""
+    res = np.array([resident.get(b, 0) for b in range(_native.NBINS)], np.int64)
+    rows = np.zeros((_native.NBINS, 3), np.int32)
+    n, fork = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    bs = None if bin_start is None else np.ascontiguousarray(bin_start, np.int64)
+    _native.check(_native.load_library().bce_plan_schedule(
+        _native.ptr(bs), _native.MODE_EXACT if mode == "exact" else _native.MODE_FAST, _native.ptr(res),
+        _native.ptr(rows), _native.ptr(n), _native.ptr(fork)), "plan_schedule")
+    return [tuple(r) for r in rows[:int(n[0])].tolist()], bool(fork[0])
+
+
 def _rank_main_us(cnt: np.ndarray, mode: str, cost: np.ndarray) -> float:
     """Modelled main-stream time (us) of a rank holding cnt[b] markets of each bin."""
-    c = lambda b0, b1: float(cnt[b0:b1 + 1].sum())  # noqa: E731
-    few = lambda b0, b1: 0 < c(b0, b1) < _MERGE_ROUNDS * _RESIDENT[b1]  # noqa: E731
-    lo = {b: b for b in range(4, 13)}
-    for b in (9, 11):
-        if mode == "exact" or few(b - 1, b):
-            lo[b] = b - 1
-    if few(4, 6):
-        lo[6] = 4
-    merged = {k for b in lo for k in range(lo[b], b)}
+    bin_start = np.zeros(len(cnt) + 1, np.int64)
+    bin_start[1:] = np.cumsum(cnt)
     mc = _MERGED_COST_US["exact" if mode == "exact" else "fast"]
     t = 0.0
-    for b in range(4, 13):
-        if b in merged or c(lo[b], b) == 0:
-            continue
-        t += _LAUNCH_US + cnt[b] * cost[b] + sum(cnt[k] * mc.get(k, cost[k]) for k in range(lo[b], b))
+    for b0, b, side in sorted(plan_schedule(bin_start, mode)[0], key=lambda r: r[1]):  # summed in bin order
+        if not side:
+            t += _LAUNCH_US + cnt[b] * cost[b] + sum(cnt[k] * mc.get(k, cost[k]) for k in range(b0, b))
     return t
 
 

@@ -1,7 +1,8 @@
-// consensus.hip -- batched core.compute_consensus (core.py:63-179) over CSR markets: every
-// kernel except the LDS-table one (consensus_tab.hip), the launchers and the C ABI.
+// consensus.hip -- batched core.compute_consensus (core.py:63-179) over CSR markets: the
+// seg / lpm / flat / pipe / long kernels and their launchers (the LDS-table kernel is
+// consensus_tab.hip, the wide one consensus_wide.hip; the C entries are consensus_api.hip).
 //
-// Kernels by market length (launch_seg_for_len / launch_wide_for_len pick them):
+// Kernels by market length (launch_seg_for_len / launch_wide_len pick them):
 //  consensus_pipe_kernel<G>    contiguous markets, n <= G in {8,16,32}, S <= 16384: one
 //                              loader wave streams tiles into an LDS ring (LDS-DMA), four
 //                              compute waves (lane = market) sort keys in VGPRs and walk
@@ -25,10 +26,11 @@
 #include <algorithm>
 
 #include "consensus_common.hpp"
+#include "plan_host.hpp"
 
 #pragma clang fp contract(off)
 
-constexpr int kSegWPE = 1;    // __launch_bounds__ min waves per SIMD for the segment kernel
+constexpr int kSegWPE = 1;   // __launch_bounds__ min waves per SIMD for the segment kernel
 constexpr int kFlatTM = 64;   // flat kernel: markets per wave tile
 constexpr int kFlatRing = 8;  // flat kernel: relconf gathers in flight per lane
 constexpr int kFlatWPE = 1;   // flat kernel: min waves per SIMD (register budget)
@@ -1257,7 +1259,6 @@ void consensus_pipe_kernel(ConsArgs a) {
 // long markets: workgroup per market
 // ------------------------------------------------------------------------------------
 constexpr int kLongThreads = 256;
-constexpr int kLongMaxLds = 4096;
 
 // Fixed-order (deterministic) tree sum over the workgroup (BCE_MODE_FAST).
 __device__ __forceinline__ double block_sum_tree(double v, double* red) {
@@ -1470,56 +1471,45 @@ __global__ __launch_bounds__(kLongThreads) void consensus_long_kernel(ConsArgs a
 namespace bce {
 namespace {
 
+// A persistent grid: min(units, CUs x workgroups per CU) workgroups, all resident at once,
+// the units (tiles) dealt round-robin inside the kernel.  `fallback`: workgroups per CU when
+// the occupancy query fails.
+int launch_persistent(void (*kernel)(ConsArgs), int threads, int fallback, int64_t units, const char* name,
+                      const ConsArgs& a, hipStream_t st) {
+  if (units == 0) return BCE_OK;
+  const int per_cu = blocks_per_cu(reinterpret_cast<const void*>(kernel), threads, 0, fallback, name);
+  const int64_t cap = (int64_t)cu_count() * per_cu;
+  const int grid = (int)(units < cap ? units : cap);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, st, a);
+  return check_launch(name);
+}
+
+int64_t ceil_div(int64_t n, int64_t d) { return (n + d - 1) / d; }
+
 template <int G, int TM>
 int launch_seg(const ConsArgs& a, hipStream_t st) {
-  const int64_t tiles = (a.n_list + TM - 1) / TM;
-  if (tiles == 0) return BCE_OK;
-  // persistent grid: every workgroup resident at once, tiles dealt round-robin
-  const int per_cu = blocks_per_cu(reinterpret_cast<const void*>(&consensus_seg_kernel<G, TM>), 64, 0, 8);
-  const int64_t cap = (int64_t)cu_count() * per_cu;
-  const int grid = (int)(tiles < cap ? tiles : cap);
-  hipLaunchKernelGGL((consensus_seg_kernel<G, TM>), dim3(grid), dim3(64), 0, st, a);
-  return check_launch("consensus_seg_kernel");
+  return launch_persistent(consensus_seg_kernel<G, TM>, 64, 8, ceil_div(a.n_list, TM), "consensus_seg_kernel", a, st);
 }
 
 template <int G>
 int launch_lpm(const ConsArgs& a, hipStream_t st) {
-  const int64_t tiles = (a.n_list + kWave - 1) / kWave;
-  if (tiles == 0) return BCE_OK;
-  const int per_cu = blocks_per_cu(reinterpret_cast<const void*>(&consensus_lpm_kernel<G>), 64, 0, 4);
-  const int64_t cap = (int64_t)cu_count() * per_cu;
-  const int grid = (int)(tiles < cap ? tiles : cap);
-  hipLaunchKernelGGL((consensus_lpm_kernel<G>), dim3(grid), dim3(64), 0, st, a);
-  return check_launch("consensus_lpm_kernel");
+  return launch_persistent(consensus_lpm_kernel<G>, 64, 4, ceil_div(a.n_list, kWave), "consensus_lpm_kernel", a, st);
 }
 
 template <int G>
 int launch_pipe(const ConsArgs& a, hipStream_t st) {
-  constexpr int TM = 64;
-  const int64_t tiles = (a.n_list + TM - 1) / TM;
-  if (tiles == 0) return BCE_OK;
-  const int per_cu = blocks_per_cu(reinterpret_cast<const void*>(&consensus_pipe_kernel<G>),
-                                   64 * (PipeCfg<G>::C + PipeCfg<G>::L), 0, 1, "consensus_pipe_kernel");
-  const int64_t cap = (int64_t)cu_count() * per_cu;
-  const int grid = (int)(tiles < cap ? tiles : cap);
-  hipLaunchKernelGGL((consensus_pipe_kernel<G>), dim3(grid), dim3(64 * (PipeCfg<G>::C + PipeCfg<G>::L)), 0, st,
-                     a);
-  return check_launch("consensus_pipe_kernel");
+  return launch_persistent(consensus_pipe_kernel<G>, 64 * (PipeCfg<G>::C + PipeCfg<G>::L), 1, ceil_div(a.n_list, 64),
+                           "consensus_pipe_kernel", a, st);
 }
 
 template <int G>
 int launch_flat(const ConsArgs& a, hipStream_t st) {
   constexpr int TM = kFlatTM, WPB = kFlatWPB;
-  const int64_t tiles = (a.n_list + TM - 1) / TM;
-  if (tiles == 0) return BCE_OK;
-  const int per_cu = blocks_per_cu(reinterpret_cast<const void*>(&consensus_flat_kernel<G, TM, WPB>), 64 * WPB, 0, 2,
-                                   "consensus_flat_kernel");
-  const int64_t blocks = (tiles + WPB - 1) / WPB;
-  const int64_t cap = (int64_t)cu_count() * per_cu;
-  const int grid = (int)(blocks < cap ? blocks : cap);
-  hipLaunchKernelGGL((consensus_flat_kernel<G, TM, WPB>), dim3(grid), dim3(64 * WPB), 0, st, a);
-  return check_launch("consensus_flat_kernel");
+  return launch_persistent(consensus_flat_kernel<G, TM, WPB>, 64 * WPB, 2, ceil_div(ceil_div(a.n_list, TM), WPB),
+                           "consensus_flat_kernel", a, st);
 }
+
+}  // namespace
 
 // Markets with n <= 64 (a.list == NULL: contiguous CSR; else a planned market list).
 //   contiguous, 16 < n <= 32, S <= kTabMaxSources   consensus_tab32_kernel (table in LDS)
@@ -1554,891 +1544,13 @@ int launch_long_lds(const ConsArgs& a, hipStream_t st) {
   return check_launch("consensus_long_kernel<lds>");
 }
 
-// Markets with 64 < n <= 4096: the register-sort kernel (consensus_wide.hip), with packed
-// 32-bit (sid, index) keys when they fit and 64-bit keys for larger tables.
-int launch_wide_for_len(int64_t max_len, const ConsArgs& a, hipStream_t st) {
-  return launch_wide_len(max_len, a, st);
-}
-
-constexpr int kHugeGrid = 512;
-
-int64_t next_pow2(int64_t n) {
-  int64_t p = 1;
-  while (p < n) p <<= 1;
-  return p;
-}
-
-int launch_long_global(ConsArgs a, int64_t max_len, void* scratch, int64_t scratch_bytes,
-                       hipStream_t st) {
+int launch_long_global(ConsArgs a, void* scratch, int64_t stride, hipStream_t st) {
   if (a.n_list == 0) return BCE_OK;
-  const int grid = (int)(a.n_list < kHugeGrid ? a.n_list : kHugeGrid);
-  const int64_t P = next_pow2(max_len);
-  const int64_t need = (int64_t)grid * 4 * P * 8;
-  BCE_REQUIRE(scratch && scratch_bytes >= need, "consensus: scratch too small (%lld < %lld)",
-              (long long)scratch_bytes, (long long)need);
   a.scratch = scratch;
-  a.scratch_stride = P;
-  hipLaunchKernelGGL((consensus_long_kernel<false>), dim3(grid), dim3(kLongThreads), 0, st, a);
+  a.scratch_stride = stride;
+  hipLaunchKernelGGL((consensus_long_kernel<false>), dim3((int)long_scratch_grid(a.n_list)), dim3(kLongThreads), 0,
+                     st, a);
   return check_launch("consensus_long_kernel<global>");
 }
 
-__global__ void max_len_kernel(const int64_t* offsets, int64_t n, const int32_t* list, int64_t n_list,
-                               unsigned long long* out) {
-  int64_t best = 0;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_list;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t m = list ? list[i] : i;
-    const int64_t len = offsets[m + 1] - offsets[m];
-    best = len > best ? len : best;
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    const int64_t x = __shfl_xor(best, o);
-    best = x > best ? x : best;
-  }
-  if ((threadIdx.x & 63) == 0) atomicMax(out, (unsigned long long)best);
-}
-
-int check_common(const int64_t* offsets, int64_t n_markets, const int32_t* sid, const double* prob,
-                 const double* relconf, const uint32_t* present_bits, int32_t n_sources,
-                 double* consensus, double* confidence, double* total_weight, int32_t* n_unique) {
-  BCE_REQUIRE(n_markets >= 0, "consensus: n_markets < 0");
-  BCE_REQUIRE(n_markets == 0 || offsets, "consensus: offsets is NULL");
-  BCE_REQUIRE(n_markets == 0 || (consensus && confidence && total_weight && n_unique),
-              "consensus: per-market outputs must be non-NULL");
-  BCE_REQUIRE(n_sources >= 0 && (n_sources == 0 || (relconf && present_bits)),
-              "consensus: source table is NULL");
-  BCE_REQUIRE((uintptr_t)relconf % 16 == 0, "consensus: relconf must be 16-byte aligned");
-  (void)sid;
-  (void)prob;
-  return BCE_OK;
-}
-
-}  // namespace
 }  // namespace bce
-
-using namespace bce;
-
-extern "C" int bce_consensus_csr(const int64_t* offsets, int64_t n_markets, const int32_t* sid,
-                                 const double* prob, int64_t n_signals, const double* relconf,
-                                 const uint32_t* present_bits, int32_t n_sources,
-                                 const int32_t* market_list, int64_t n_list, int32_t max_len,
-                                 int32_t mode, double* consensus, double* confidence,
-                                 double* total_weight, int32_t* n_unique, int32_t* err_idx,
-                                 int32_t* usid, double* weight, double* nweight, void* stream) {
-  int rc = check_common(offsets, n_markets, sid, prob, relconf, present_bits, n_sources, consensus,
-                        confidence, total_weight, n_unique);
-  if (rc) return rc;
-  BCE_REQUIRE(mode == BCE_MODE_EXACT || mode == BCE_MODE_FAST, "consensus: bad mode %d", mode);
-  BCE_REQUIRE(n_signals == 0 || (sid && prob), "consensus: sid/prob NULL");
-  hipStream_t st = as_stream(stream);
-  ConsArgs a{};
-  a.offsets = offsets; a.sid = sid; a.prob = prob;
-  a.relconf = reinterpret_cast<const double2*>(relconf); a.pbits = present_bits;
-  a.n_sources = n_sources; a.n_signals = n_signals;
-  a.list = market_list; a.n_list = market_list ? n_list : n_markets;
-  a.consensus = consensus; a.confidence = confidence; a.total_weight = total_weight;
-  a.n_unique = n_unique; a.err_idx = err_idx; a.usid = usid; a.weight = weight; a.nweight = nweight;
-  a.mode = mode;
-  a.fault = fault_word();
-  a.spin_cap = spin_cap();
-  if (a.n_list == 0) return BCE_OK;
-  int64_t L = max_len;
-  if (L <= 0) {  // unknown: measure on device (synchronises)
-    unsigned long long* d = nullptr;
-    BCE_HIP(hipMallocAsync((void**)&d, sizeof(unsigned long long), st));
-    BCE_HIP(hipMemsetAsync(d, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(max_len_kernel, dim3(256), dim3(256), 0, st, offsets, n_markets, market_list,
-                       a.n_list, d);
-    unsigned long long h = 0;
-    BCE_HIP(hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, st));
-    BCE_HIP(hipFreeAsync(d, st));
-    BCE_HIP(hipStreamSynchronize(st));
-    L = (int64_t)h;
-  }
-  // the 32-bit (sid, index) key of the segment kernel needs sid < 2^(31 - log2 G)
-  if (L <= 64 && n_sources <= (1 << 25)) return launch_seg_for_len((int)(L < 1 ? 1 : L), a, st);
-  if (L <= kLongMaxLds) return launch_wide_for_len(L, a, st);
-  const int grid = (int)(a.n_list < kHugeGrid ? a.n_list : kHugeGrid);
-  const int64_t bytes = (int64_t)grid * 4 * next_pow2(L) * 8;
-  void* scratch = nullptr;
-  BCE_HIP(hipMallocAsync(&scratch, (size_t)bytes, st));
-  rc = launch_long_global(a, L, scratch, bytes, st);
-  BCE_HIP(hipFreeAsync(scratch, st));
-  return rc;
-}
-
-static_assert(BCE_NBINS == 13, "bin table");
-static constexpr int64_t kBinMax[BCE_NBINS - 1] = {8, 16, 32, 64, 128, 256, 512, 1024, 1536, 2048, 3072, kLongMaxLds};
-constexpr int kBinNp2Lo = 8, kBinNp2Hi = 10;  // the 1536 and 3072 bins
-static_assert(kBinMax[kBinNp2Lo] == 1536 && kBinMax[kBinNp2Hi] == 3072, "non-power-of-two bins");
-constexpr int kPlanSideLast = 3;  // bins 0..3 (n <= 64) run on the side stream
-constexpr double kMergeRounds = 6.0;  // merge a small call's bins below this many resident rounds
-static int bin_of(int64_t n) {
-  for (int b = 0; b < BCE_NBINS - 1; ++b)
-    if (n <= kBinMax[b]) return b;
-  return BCE_NBINS - 1;
-}
-
-extern "C" int bce_plan_bins(const int64_t* offsets_host, int64_t n_markets, int32_t* order_host,
-                             int64_t* bin_start_host, int32_t* max_len_host) {
-  BCE_REQUIRE(n_markets >= 0 && offsets_host && order_host && bin_start_host,
-              "plan_bins: NULL argument");
-  int64_t cnt[BCE_NBINS] = {0};
-  int64_t mx = 0;
-  for (int64_t m = 0; m < n_markets; ++m) {
-    const int64_t n = offsets_host[m + 1] - offsets_host[m];
-    BCE_REQUIRE(n >= 0, "plan_bins: offsets not monotone at market %lld", (long long)m);
-    cnt[bin_of(n)]++;
-    mx = n > mx ? n : mx;
-  }
-  bin_start_host[0] = 0;
-  for (int b = 0; b < BCE_NBINS; ++b) bin_start_host[b + 1] = bin_start_host[b] + cnt[b];
-  int64_t pos[BCE_NBINS];
-  for (int b = 0; b < BCE_NBINS; ++b) pos[b] = bin_start_host[b];
-  for (int64_t m = 0; m < n_markets; ++m) {
-    const int64_t n = offsets_host[m + 1] - offsets_host[m];
-    order_host[pos[bin_of(n)]++] = (int32_t)m;
-  }
-  // Wide bins (65..4096) longest market first (LPT order, ties by market index): a
-  // persistent workgroup takes its next market as it finishes one, so the last round of
-  // workgroups gets the short ones and the launch's tail shrinks (C3 fast -0.7%, exact
-  // -0.6%, one of 8 market shards -1.3%: profiles/r03ae/).
-  for (int b = kPlanSideLast + 1; b < BCE_NBINS - 1; ++b)
-    std::stable_sort(order_host + bin_start_host[b], order_host + bin_start_host[b + 1], [&](int32_t x, int32_t y) {
-      return offsets_host[x + 1] - offsets_host[x] > offsets_host[y + 1] - offsets_host[y];
-    });
-  if (max_len_host) *max_len_host = (int32_t)(mx > 0x7fffffff ? 0x7fffffff : mx);
-  return BCE_OK;
-}
-
-extern "C" int64_t bce_consensus_scratch_bytes(const int64_t* offsets_host, const int32_t* order_host,
-                                               const int64_t* bin_start_host) {
-  const int64_t b0 = bin_start_host[BCE_NBINS - 1], b1 = bin_start_host[BCE_NBINS];
-  if (b1 <= b0) return 0;
-  int64_t mx = 0;
-  for (int64_t i = b0; i < b1; ++i) {
-    const int32_t m = order_host[i];
-    const int64_t n = offsets_host[m + 1] - offsets_host[m];
-    mx = n > mx ? n : mx;
-  }
-  const int64_t cnt = b1 - b0;
-  const int grid = (int)(cnt < kHugeGrid ? cnt : kHugeGrid);
-  return (int64_t)grid * 4 * next_pow2(mx) * 8;
-}
-
-// ======================================================================================
-// The device planner (bce_plan_bins_device): the plan of bce_plan_bins built from device
-// offsets, no D2H copy of the CSR.  A market's bin and its LPT position are one 12-bit key
-//   bins 0..3 (n <= 64)           key = bin                (market order inside the bin)
-//   wide bin b, lengths lo..hi    key = 4 + (lo - 65) + (hi - n)   (bins ascending, longest first)
-//   n > 4096                      key = kPlanKeys - 1
-// so the plan is a STABLE sort of the market indices by key: two LSD passes of 6-bit digits,
-// each a per-chunk digit count, one exclusive scan of the [digit][chunk] counts and a stable
-// scatter (the rank inside a chunk from a [thread][digit] count matrix in LDS).  Stable at
-// every pass, hence market order inside equal keys: exactly bce_plan_bins' order.
-// ======================================================================================
-namespace bce {
-constexpr int kPlanKeys = 4 + (4096 - 65 + 1) + 1;  // 4037 < 2^12
-constexpr int kPlanThreads = 256;
-constexpr int kPlanPer = 4;                          // markets per thread
-constexpr int kPlanChunk = kPlanThreads * kPlanPer;  // markets per workgroup
-constexpr int kPlanDigits = 64;                      // 6-bit digits, two passes
-constexpr int kPlanScanThreads = 1024;
-static_assert(kPlanKeys <= kPlanDigits * kPlanDigits, "two 6-bit passes");
-
-struct PlanInfo {
-  unsigned long long bins[BCE_NBINS];
-  unsigned long long max_len;
-  unsigned long long long_max;  // longest market of the > 4096 bin (scratch sizing)
-  unsigned long long badrev;    // M - (first market whose offsets decrease), 0 = none
-};
-
-__device__ __forceinline__ int plan_bin(int64_t n) {
-  return n <= 8 ? 0 : n <= 16 ? 1 : n <= 32 ? 2 : n <= 64 ? 3 : n <= 128 ? 4 : n <= 256 ? 5 : n <= 512 ? 6
-       : n <= 1024 ? 7 : n <= 1536 ? 8 : n <= 2048 ? 9 : n <= 3072 ? 10 : n <= 4096 ? 11 : 12;
-}
-
-__device__ __forceinline__ int plan_key(int64_t n, int b) {
-  if (b <= 3) return b;
-  if (b == 12) return kPlanKeys - 1;
-  const int lo = b == 4 ? 65 : b == 5 ? 129 : b == 6 ? 257 : b == 7 ? 513 : b == 8 ? 1025 : b == 9 ? 1537
-               : b == 10 ? 2049 : 3073;
-  const int hi = b == 4 ? 128 : b == 5 ? 256 : b == 6 ? 512 : b == 7 ? 1024 : b == 8 ? 1536 : b == 9 ? 2048
-               : b == 10 ? 3072 : 4096;
-  return 4 + (lo - 65) + (hi - (int)n);
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_max_u64(T v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const T o = (T)__shfl_xor((unsigned long long)v, m);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
-// Pass PASS digit counts of chunk blockIdx.x -> counts[digit * nchunks + chunk].  Pass 0 reads
-// the offsets (striped: coalesced) and also writes the chunk's record for PlanInfo (bin counts,
-// longest market, longest > 4096 market, first decreasing offset) -- no global atomics: the
-// pass-0 scan reduces the records (800 same-address atomicMax per call cost ~10 us).
-constexpr int kPlanRec = 16;  // int64 per chunk record: bins[13], max_len, long_max, badrev
-template <int PASS, bool CM>
-__global__ __launch_bounds__(kPlanThreads) void plan_count_kernel(const int64_t* __restrict__ offsets, int64_t M,
-                                                                  const uint16_t* __restrict__ keys_in,
-                                                                  int32_t* __restrict__ counts, int64_t nchunks,
-                                                                  int64_t* __restrict__ crec) {
-  __shared__ int cnt[kPlanDigits];
-  __shared__ int bincnt[BCE_NBINS];
-  __shared__ unsigned long long wmax[kPlanThreads / kWave][3];
-  const int t = threadIdx.x;
-  const int64_t c = blockIdx.x;
-  if (t < kPlanDigits) cnt[t] = 0;
-  if (PASS == 0 && t < BCE_NBINS) bincnt[t] = 0;
-  __syncthreads();
-  unsigned long long mx = 0, lmx = 0, badrev = 0;
-#pragma unroll
-  for (int k = 0; k < kPlanPer; ++k) {
-    const int64_t i = c * kPlanChunk + k * kPlanThreads + t;
-    if (i < M) {
-      int key;
-      if constexpr (PASS == 0) {
-        const int64_t n = offsets[i + 1] - offsets[i];
-        if (n < 0) badrev = (unsigned long long)(M - i) > badrev ? (unsigned long long)(M - i) : badrev;
-        const int b = plan_bin(n);
-        key = plan_key(n < 0 ? 0 : n, n < 0 ? 0 : b);
-        atomicAdd(&bincnt[n < 0 ? 0 : b], 1);
-        const unsigned long long un = n < 0 ? 0ull : (unsigned long long)n;
-        mx = un > mx ? un : mx;
-        if (b == 12) lmx = un > lmx ? un : lmx;
-      } else {
-        key = keys_in[i];
-      }
-      atomicAdd(&cnt[(key >> (6 * PASS)) & (kPlanDigits - 1)], 1);
-    }
-  }
-  if constexpr (PASS == 0) {
-    mx = wave_max_u64(mx);
-    lmx = wave_max_u64(lmx);
-    badrev = wave_max_u64(badrev);
-    if (lane_id() == 0) {
-      wmax[t / kWave][0] = mx;
-      wmax[t / kWave][1] = lmx;
-      wmax[t / kWave][2] = badrev;
-    }
-  }
-  __syncthreads();
-  if (t < kPlanDigits) counts[CM ? c * kPlanDigits + t : (int64_t)t * nchunks + c] = cnt[t];
-  if constexpr (PASS == 0) {
-    int64_t* r = crec + c * kPlanRec;
-    if (t < BCE_NBINS) r[t] = bincnt[t];
-    if (t >= BCE_NBINS && t < BCE_NBINS + 3) {
-      unsigned long long v = 0;
-      for (int w = 0; w < kPlanThreads / kWave; ++w) v = wmax[w][t - BCE_NBINS] > v ? wmax[w][t - BCE_NBINS] : v;
-      r[t] = (int64_t)v;
-    }
-  }
-}
-
-// Reduce the count pass's chunk records into PlanInfo; with bin_start_dev also the device bin
-// boundaries and the device-driven faults (decreasing offsets: every bin empty + kFaultOffsets;
-// raise_long: a market > 4096 raises kFaultTooLong).  Called by one whole workgroup.
-__device__ __forceinline__ void plan_reduce_info(const int64_t* __restrict__ crec, int64_t nchunks, PlanInfo* info,
-                                                 int64_t* bin_start_dev, int* fault, int raise_long,
-                                                 unsigned long long* sacc, int t, int nthreads) {
-  if (t < BCE_NBINS + 3) sacc[t] = 0;
-  __syncthreads();
-  unsigned long long b[BCE_NBINS] = {}, m0 = 0, m1 = 0, m2 = 0;
-  for (int64_t c = t; c < nchunks; c += nthreads) {
-    const int64_t* r = crec + c * kPlanRec;
-#pragma unroll
-    for (int k = 0; k < BCE_NBINS; ++k) b[k] += (unsigned long long)r[k];
-    m0 = (unsigned long long)r[BCE_NBINS] > m0 ? (unsigned long long)r[BCE_NBINS] : m0;
-    m1 = (unsigned long long)r[BCE_NBINS + 1] > m1 ? (unsigned long long)r[BCE_NBINS + 1] : m1;
-    m2 = (unsigned long long)r[BCE_NBINS + 2] > m2 ? (unsigned long long)r[BCE_NBINS + 2] : m2;
-  }
-  // wave reductions first: one LDS atomic per wave and counter
-#pragma unroll
-  for (int k = 0; k < BCE_NBINS; ++k) {
-    unsigned long long v = b[k];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += (unsigned long long)__shfl_xor((long long)v, o);
-    b[k] = v;
-  }
-  m0 = wave_max_u64(m0);
-  m1 = wave_max_u64(m1);
-  m2 = wave_max_u64(m2);
-  if (lane_id() == 0) {
-#pragma unroll
-    for (int k = 0; k < BCE_NBINS; ++k)
-      if (b[k]) atomicAdd(&sacc[k], b[k]);
-    if (m0) atomicMax(&sacc[BCE_NBINS], m0);
-    if (m1) atomicMax(&sacc[BCE_NBINS + 1], m1);
-    if (m2) atomicMax(&sacc[BCE_NBINS + 2], m2);
-  }
-  __syncthreads();
-  if (t == 0) {
-    for (int k = 0; k < BCE_NBINS; ++k) info->bins[k] = sacc[k];
-    info->max_len = sacc[BCE_NBINS];
-    info->long_max = sacc[BCE_NBINS + 1];
-    info->badrev = sacc[BCE_NBINS + 2];
-    if (bin_start_dev) {
-      const bool bad = sacc[BCE_NBINS + 2] != 0;
-      int64_t run = 0;
-      bin_start_dev[0] = 0;
-      for (int k = 0; k < BCE_NBINS; ++k) {
-        run += bad ? 0 : (int64_t)sacc[k];
-        bin_start_dev[k + 1] = run;
-      }
-      if (fault && bad) atomicCAS(fault, 0, kFaultOffsets);
-      if (fault && !bad && raise_long && sacc[BCE_NBINS - 1]) atomicCAS(fault, 0, kFaultTooLong);
-    }
-  }
-}
-
-// In-place exclusive scan of counts[0..E) by one workgroup (E = 64 x chunks), in tiles of 8
-// consecutive counts per thread (the loads of a tile in flight together).  INFO (pass 0): also
-// reduces the chunk records into PlanInfo and, with bin_start_dev, writes the device bin
-// boundaries (decreasing offsets: every bin empty + kFaultOffsets; raise_long: a market > 4096
-// raises kFaultTooLong -- the device-driven launch does not compute those).
-template <bool INFO>
-__global__ __launch_bounds__(kPlanScanThreads) void plan_scan_kernel(int32_t* __restrict__ counts, int64_t E,
-                                                                     const int64_t* __restrict__ crec, int64_t nchunks,
-                                                                     PlanInfo* info, int64_t* bin_start_dev, int* fault,
-                                                                     int raise_long) {
-  constexpr int V = 8;
-  constexpr int NW = kPlanScanThreads / kWave;
-  __shared__ int64_t wsum[NW];
-  __shared__ int64_t tile_total;
-  __shared__ unsigned long long sacc[BCE_NBINS + 3];
-  const int t = threadIdx.x;
-  const int w = t / kWave;
-  if constexpr (INFO) plan_reduce_info(crec, nchunks, info, bin_start_dev, fault, raise_long, sacc, t, kPlanScanThreads);
-  int64_t carry = 0;
-  for (int64_t base = 0; base < E; base += (int64_t)kPlanScanThreads * V) {
-    const int64_t i0 = base + (int64_t)t * V;
-    int v[V];
-    int64_t s = 0;
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      v[k] = (i0 + k < E) ? counts[i0 + k] : 0;
-      s += v[k];
-    }
-    int64_t inc = s;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const int64_t o = __shfl_up(inc, d);
-      if (lane_id() >= d) inc += o;
-    }
-    if (lane_id() == kWave - 1) wsum[w] = inc;
-    __syncthreads();
-    if (t == 0) {
-      int64_t run = 0;
-      for (int k = 0; k < NW; ++k) {
-        const int64_t x = wsum[k];
-        wsum[k] = run;
-        run += x;
-      }
-      tile_total = run;
-    }
-    __syncthreads();
-    int64_t run = carry + wsum[w] + inc - s;
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      if (i0 + k < E) counts[i0 + k] = (int32_t)run;
-      run += v[k];
-    }
-    carry += tile_total;
-    __syncthreads();  // wsum / tile_total are rewritten by the next tile
-  }
-}
-
-// Stable scatter of chunk blockIdx.x by its pass-PASS digit.  Thread t holds markets
-// 4t..4t+3 of the chunk (blocked: thread order == input order); mat[t][d] counts thread t's
-// items of digit d, and its exclusive scan in (d, t) order gives every item its rank among the
-// chunk's items of smaller digit or equal digit and earlier position.
-// INKB (<= kPlanInkbMax chunks): the counts are chunk-major [chunk][digit] and every workgroup
-// derives its own 64 bases from all of them (a wave reads one 256-B chunk row per step), so no
-// scan launch sits between the passes; PASS 0 runs one extra workgroup that reduces the chunk
-// records (plan_reduce_info) alongside.  Otherwise `base` is the digit-major exclusive scan of plan_scan_kernel.
-constexpr int64_t kPlanInkbMax = 1024;
-template <int PASS, bool INKB>
-__global__ __launch_bounds__(kPlanThreads) void plan_scatter_kernel(const int64_t* __restrict__ offsets, int64_t M,
-                                                                    const uint16_t* __restrict__ keys_in,
-                                                                    const int32_t* __restrict__ idx_in,
-                                                                    const int32_t* __restrict__ base, int64_t nchunks,
-                                                                    uint16_t* __restrict__ keys_out,
-                                                                    int32_t* __restrict__ idx_out,
-                                                                    const int64_t* __restrict__ crec, PlanInfo* info,
-                                                                    int64_t* bin_start_dev, int* fault, int raise_long) {
-  __shared__ int mat[kPlanThreads * kPlanDigits];  // [t][d], 64 KB
-  __shared__ int part[kPlanThreads];
-  __shared__ int sTot[kPlanDigits], sPre[kPlanDigits];
-  __shared__ unsigned long long sacc[BCE_NBINS + 3];
-  const int t = threadIdx.x;
-  const int64_t c = blockIdx.x;
-  if constexpr (INKB) {
-    if (PASS == 0 && c == nchunks) {  // the extra workgroup of pass 0: PlanInfo, in parallel with the scatter
-      plan_reduce_info(crec, nchunks, info, bin_start_dev, fault, raise_long, sacc, t, kPlanThreads);
-      return;
-    }
-    if (t < kPlanDigits) {
-      sTot[t] = 0;
-      sPre[t] = 0;
-    }
-    __syncthreads();
-    const int dd = t & (kPlanDigits - 1), qq = t / kPlanDigits;
-    int tot = 0, pre = 0;
-#pragma unroll 4
-    for (int64_t c2 = qq; c2 < nchunks; c2 += kPlanThreads / kPlanDigits) {
-      const int v = base[c2 * kPlanDigits + dd];
-      tot += v;
-      pre += (c2 < c) ? v : 0;
-    }
-    atomicAdd(&sTot[dd], tot);
-    atomicAdd(&sPre[dd], pre);
-    __syncthreads();
-    if (t < kWave) {  // exclusive scan of the digit totals (one wave, lane = digit), + this chunk's prefix
-      const int v = sTot[t];
-      int inc = v;
-#pragma unroll
-      for (int o = 1; o < kWave; o <<= 1) {
-        const int y = __shfl_up(inc, o);
-        if (lane_id() >= o) inc += y;
-      }
-      sPre[t] += inc - v;
-    }
-  }
-#pragma unroll 8
-  for (int j = 0; j < kPlanDigits; ++j) mat[j * kPlanThreads + t] = 0;
-  int key[kPlanPer], idx[kPlanPer], before[kPlanPer];
-  const int64_t i0 = c * kPlanChunk + (int64_t)t * kPlanPer;
-#pragma unroll
-  for (int k = 0; k < kPlanPer; ++k) {
-    const int64_t i = i0 + k;
-    key[k] = -1;
-    idx[k] = 0;
-    if (i < M) {
-      if constexpr (PASS == 0) {
-        int64_t n = offsets[i + 1] - offsets[i];
-        n = n < 0 ? 0 : n;
-        key[k] = plan_key(n, plan_bin(n));
-        idx[k] = (int)i;
-      } else {
-        key[k] = keys_in[i];
-        idx[k] = idx_in[i];
-      }
-    }
-  }
-  __syncthreads();
-  int* row = mat + t * kPlanDigits;
-#pragma unroll
-  for (int k = 0; k < kPlanPer; ++k) {
-    if (key[k] >= 0) {
-      const int d = (key[k] >> (6 * PASS)) & (kPlanDigits - 1);
-      before[k] = row[d];
-      row[d] = before[k] + 1;
-    }
-  }
-  __syncthreads();
-  // column sums: thread j = (q, d) sums mat[64q .. 64q+63][d] (a wave reads consecutive words)
-  const int d = t & (kPlanDigits - 1), q = t / kPlanDigits;
-  int s = 0;
-#pragma unroll 8
-  for (int r = 0; r < kPlanDigits; ++r) s += mat[(q * kPlanDigits + r) * kPlanDigits + d];
-  part[d * (kPlanThreads / kPlanDigits) + q] = s;
-  __syncthreads();
-  if (t < kWave) {  // exclusive scan of part[] (256 values, 4 per lane) by one wave
-    int v[4], sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { v[k] = part[4 * t + k]; sum += v[k]; }
-    int inc = sum;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const int y = __shfl_up(inc, o);
-      if (lane_id() >= o) inc += y;
-    }
-    int run = inc - sum;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { part[4 * t + k] = run; run += v[k]; }
-  }
-  __syncthreads();
-  int run = part[d * (kPlanThreads / kPlanDigits) + q];
-#pragma unroll 8
-  for (int r = 0; r < kPlanDigits; ++r) {
-    int* p = &mat[(q * kPlanDigits + r) * kPlanDigits + d];
-    const int v = *p;
-    *p = run;
-    run += v;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < kPlanPer; ++k) {
-    if (key[k] >= 0) {
-      const int dg = (key[k] >> (6 * PASS)) & (kPlanDigits - 1);
-      const int64_t pos = (INKB ? (int64_t)sPre[dg] : (int64_t)base[(int64_t)dg * nchunks + c]) + (row[dg] - mat[dg]) +
-                          before[k];
-      if constexpr (PASS == 0) keys_out[pos] = (uint16_t)key[k];
-      idx_out[pos] = idx[k];
-    }
-  }
-}
-}  // namespace bce
-
-static int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-static int plan_device_launch(const int64_t* offsets, int64_t n_markets, int32_t* order, void* scratch,
-                              hipStream_t st, PlanInfo** info_out, int64_t* bin_start_dev, int raise_long);
-
-extern "C" int64_t bce_plan_device_scratch_bytes(int64_t n_markets) {
-  if (n_markets <= 0) return 0;
-  const int64_t chunks = (n_markets + kPlanChunk - 1) / kPlanChunk;
-  return align256(sizeof(PlanInfo)) + align256(2 * n_markets) + align256(4 * n_markets) +
-         align256(4 * kPlanDigits * chunks) + align256(8 * kPlanRec * chunks);
-}
-
-extern "C" int bce_plan_bins_device(const int64_t* offsets, int64_t n_markets, int32_t* order,
-                                    int64_t* bin_start_host, int32_t* max_len_host,
-                                    int64_t* long_scratch_bytes_host, void* scratch, int64_t scratch_bytes,
-                                    void* stream) {
-  BCE_REQUIRE(n_markets >= 0 && n_markets < ((int64_t)1 << 31), "plan_bins_device: bad n_markets %lld",
-              (long long)n_markets);
-  BCE_REQUIRE(bin_start_host, "plan_bins_device: bin_start_host NULL");
-  if (long_scratch_bytes_host) *long_scratch_bytes_host = 0;
-  if (max_len_host) *max_len_host = 0;
-  for (int b = 0; b <= BCE_NBINS; ++b) bin_start_host[b] = 0;
-  if (n_markets == 0) return BCE_OK;
-  BCE_REQUIRE(offsets && order && scratch, "plan_bins_device: NULL argument");
-  BCE_REQUIRE(scratch_bytes >= bce_plan_device_scratch_bytes(n_markets), "plan_bins_device: scratch too small");
-  hipStream_t st = as_stream(stream);
-  PlanInfo* info = nullptr;
-  int rc = plan_device_launch(offsets, n_markets, order, scratch, st, &info, nullptr, 0);
-  if (rc) return rc;
-  PlanInfo h{};
-  BCE_HIP(hipMemcpyAsync(&h, info, sizeof h, hipMemcpyDeviceToHost, st));
-  BCE_HIP(hipStreamSynchronize(st));
-  BCE_REQUIRE(h.badrev == 0, "plan_bins: offsets not monotone at market %lld",
-              (long long)(n_markets - (int64_t)h.badrev));
-  for (int b = 0; b < BCE_NBINS; ++b) bin_start_host[b + 1] = bin_start_host[b] + (int64_t)h.bins[b];
-  if (max_len_host) *max_len_host = (int32_t)(h.max_len > 0x7fffffffull ? 0x7fffffff : h.max_len);
-  const int64_t n_long = (int64_t)h.bins[BCE_NBINS - 1];
-  if (long_scratch_bytes_host && n_long > 0) {
-    const int grid = (int)(n_long < kHugeGrid ? n_long : kHugeGrid);
-    *long_scratch_bytes_host = (int64_t)grid * 4 * next_pow2((int64_t)h.long_max) * 8;
-  }
-  return BCE_OK;
-}
-
-
-static int plan_device_launch(const int64_t* offsets, int64_t n_markets, int32_t* order, void* scratch,
-                              hipStream_t st, PlanInfo** info_out, int64_t* bin_start_dev, int raise_long) {
-  const int64_t chunks = (n_markets + kPlanChunk - 1) / kPlanChunk;
-  char* p = static_cast<char*>(scratch);
-  PlanInfo* info = reinterpret_cast<PlanInfo*>(p);
-  p += align256(sizeof(PlanInfo));
-  uint16_t* keys = reinterpret_cast<uint16_t*>(p);
-  p += align256(2 * n_markets);
-  int32_t* idx = reinterpret_cast<int32_t*>(p);
-  p += align256(4 * n_markets);
-  int32_t* counts = reinterpret_cast<int32_t*>(p);
-  p += align256(4 * kPlanDigits * chunks);
-  int64_t* crec = reinterpret_cast<int64_t*>(p);
-  const dim3 g((unsigned)chunks), blk(kPlanThreads), sg(1), sblk(kPlanScanThreads);
-  int* fw = fault_word();
-  if (chunks <= kPlanInkbMax) {  // 4 launches: bases derived inside the scatter kernels
-    hipLaunchKernelGGL((plan_count_kernel<0, true>), g, blk, 0, st, offsets, n_markets, nullptr, counts, chunks, crec);
-    hipLaunchKernelGGL((plan_scatter_kernel<0, true>), dim3((unsigned)chunks + 1), blk, 0, st, offsets, n_markets,
-                       nullptr, nullptr, counts, chunks, keys, idx, crec, info, bin_start_dev, fw, raise_long);
-    hipLaunchKernelGGL((plan_count_kernel<1, true>), g, blk, 0, st, offsets, n_markets, keys, counts, chunks, nullptr);
-    hipLaunchKernelGGL((plan_scatter_kernel<1, true>), g, blk, 0, st, offsets, n_markets, keys, idx, counts, chunks,
-                       nullptr, order, nullptr, nullptr, nullptr, nullptr, 0);
-  } else {  // huge batches: one digit-major scan launch per pass
-    hipLaunchKernelGGL((plan_count_kernel<0, false>), g, blk, 0, st, offsets, n_markets, nullptr, counts, chunks, crec);
-    hipLaunchKernelGGL((plan_scan_kernel<true>), sg, sblk, 0, st, counts, kPlanDigits * chunks, crec, chunks, info,
-                       bin_start_dev, fw, raise_long);
-    hipLaunchKernelGGL((plan_scatter_kernel<0, false>), g, blk, 0, st, offsets, n_markets, nullptr, nullptr, counts,
-                       chunks, keys, idx, nullptr, nullptr, nullptr, nullptr, 0);
-    hipLaunchKernelGGL((plan_count_kernel<1, false>), g, blk, 0, st, offsets, n_markets, keys, counts, chunks, nullptr);
-    hipLaunchKernelGGL((plan_scan_kernel<false>), sg, sblk, 0, st, counts, kPlanDigits * chunks, nullptr, (int64_t)0,
-                       nullptr, nullptr, nullptr, 0);
-    hipLaunchKernelGGL((plan_scatter_kernel<1, false>), g, blk, 0, st, offsets, n_markets, keys, idx, counts, chunks,
-                       nullptr, order, nullptr, nullptr, nullptr, nullptr, 0);
-  }
-  *info_out = info;
-  return check_launch("plan_bins_device");
-}
-
-extern "C" int bce_plan_bins_device_async(const int64_t* offsets, int64_t n_markets, int32_t* order,
-                                          int64_t* bin_start_dev, void* scratch, int64_t scratch_bytes,
-                                          void* stream) {
-  BCE_REQUIRE(n_markets >= 0 && n_markets < ((int64_t)1 << 31), "plan_bins_device_async: bad n_markets %lld",
-              (long long)n_markets);
-  BCE_REQUIRE(bin_start_dev, "plan_bins_device_async: bin_start_dev NULL");
-  hipStream_t st = as_stream(stream);
-  if (n_markets == 0) {
-    BCE_HIP(hipMemsetAsync(bin_start_dev, 0, (BCE_NBINS + 1) * sizeof(int64_t), st));
-    return BCE_OK;
-  }
-  BCE_REQUIRE(offsets && order && scratch, "plan_bins_device_async: NULL argument");
-  BCE_REQUIRE(scratch_bytes >= bce_plan_device_scratch_bytes(n_markets), "plan_bins_device_async: scratch too small");
-  PlanInfo* info = nullptr;
-  return plan_device_launch(offsets, n_markets, order, scratch, st, &info, bin_start_dev, 1);
-}
-
-extern "C" int bce_consensus_planned(const int64_t* offsets, int64_t n_markets, const int32_t* sid,
-                                     const double* prob, int64_t n_signals, const double* relconf,
-                                     const uint32_t* present_bits, int32_t n_sources,
-                                     const int32_t* order, const int64_t* bin_start_host,
-                                     int32_t mode, double* consensus, double* confidence,
-                                     double* total_weight, int32_t* n_unique, int32_t* err_idx,
-                                     int32_t* usid, double* weight, double* nweight, void* scratch,
-                                     int64_t scratch_bytes, void* stream) {
-  int rc = check_common(offsets, n_markets, sid, prob, relconf, present_bits, n_sources, consensus,
-                        confidence, total_weight, n_unique);
-  if (rc) return rc;
-  BCE_REQUIRE(bin_start_host && (order || n_markets == 0), "planned: missing plan");
-  BCE_REQUIRE(mode == BCE_MODE_EXACT || mode == BCE_MODE_FAST, "planned: bad mode %d", mode);
-  BCE_REQUIRE(n_signals == 0 || (sid && prob), "planned: sid/prob NULL");
-  hipStream_t st = as_stream(stream);
-  ConsArgs base{};
-  base.offsets = offsets; base.sid = sid; base.prob = prob;
-  base.relconf = reinterpret_cast<const double2*>(relconf); base.pbits = present_bits;
-  base.n_sources = n_sources; base.n_signals = n_signals; base.consensus = consensus; base.confidence = confidence;
-  base.total_weight = total_weight; base.n_unique = n_unique; base.err_idx = err_idx;
-  base.usid = usid; base.weight = weight; base.nweight = nweight; base.mode = mode;
-  base.fault = fault_word();
-  base.spin_cap = spin_cap();
-  const bool seg_ok = n_sources <= (1 << 25);
-  // The short-market bins (n <= 64) are small latency-bound launches: they run on a side
-  // stream while the long bins run on st, longest first (joined before return).  Measured
-  // on C3: 1.73 -> 1.65 ms; moving wide bins to the side stream too, or forking every bin
-  // over 2-8 streams, was slower (profiles/r02_c3_plan_streams.jsonl); so was dealing every
-  // bin over 2 or 4 streams with the resident grid shared out by estimated work (round 5,
-  // profiles/archive/r05b/: one 8th of C3 0.233 -> 0.294 / 0.307 ms), and a small call's 65..1024
-  // launches on a second side stream (0.2188 -> 0.2325 ms, profiles/archive/r05f/).
-  hipStream_t side = st;
-  std::unique_lock<std::mutex> fork_lock;
-  constexpr int side_last = kPlanSideLast;
-  // fork only when both streams get work: a batch of only short or only long markets runs on st
-  // alone, without the fork / join events (~10 us of step boundary)
-  const int nside = (bin_start_host[side_last + 1] > bin_start_host[0] &&
-                     bin_start_host[BCE_NBINS] > bin_start_host[side_last + 1]) ? 1 : 0;
-  rc = side_fork(st, nside, &side, &fork_lock);
-  if (rc) return rc;
-  // Launches: bin b runs with the markets of bins lo[b]..b in one kernel sized for bin b (its
-  // own markets first, then the shorter bins' -- consensus_wide_kernel's list_hi).
-  //   EXACT: the non-power-of-two bins (1025..1536, 2049..3072) always ride in the launch of the
-  //   power-of-two bin above them: the exact kernel's LDS chain buffers allow two workgroups per
-  //   CU at 3/6 waves as at 4/8, so the smaller workgroup only loses latency hiding, and a
-  //   separate launch adds a tail.
-  //   Small calls (a market shard, kMergeRounds): a launch whose markets would fill fewer than
-  //   kMergeRounds rounds of its resident grid costs a ramp and a tail for little work, so FAST
-  //   merges the non-power-of-two bins the same way and the 65..512 bins run as one 1-wave
-  //   launch -- fewer, fuller launches for a 1/8 shard of C3.
-  int lo[BCE_NBINS];
-  for (int b = 0; b < BCE_NBINS; ++b) lo[b] = b;
-  auto cnt = [&](int b0, int b1) { return bin_start_host[b1 + 1] - bin_start_host[b0]; };
-  auto few = [&](int b0, int b1) {
-    return cnt(b0, b1) > 0 && (double)cnt(b0, b1) < kMergeRounds * (double)wide_resident(kBinMax[b1], mode, n_sources);
-  };
-  for (int b : {kBinNp2Lo + 1, kBinNp2Hi + 1})
-    if (mode == BCE_MODE_EXACT || few(b - 1, b)) lo[b] = b - 1;
-  if (few(kPlanSideLast + 1, kPlanSideLast + 3)) lo[kPlanSideLast + 3] = kPlanSideLast + 1;  // 65..512 as one
-  bool merged_away[BCE_NBINS] = {};
-  for (int b = 0; b < BCE_NBINS; ++b)
-    for (int k = lo[b]; k < b; ++k) merged_away[k] = true;
-  // Launch order: longest bins first, except that the 2049..3072 bin precedes the 3073..4096
-  // one: its 6-wave workgroups leave 4 of a CU's 16 wave slots free (two per CU at 128 VGPRs),
-  // which the side stream's short-market kernels then fill (C3 fast -1.3%,
-  // profiles/archive/r03x/order_ab.txt) -- and every main-stream launch that fills fewer than
-  // kMergeRounds rounds of its resident grid (a shard's cut piece of a bin) moves behind the
-  // full ones.  A small launch first ends while the side stream still holds CUs, and the big
-  // persistent launch behind it, whose workgroups stride statically over its markets, then
-  // starts part of its grid late and drags a tail (a planned C3 shard: 0.226 vs 0.15 ms for the
-  // same bin-11 markets, profiles/r06c/).  Ordering every launch by estimated work instead cost
-  // the full C3 batch 2% (1.325 vs 1.298 ms, profiles/r06e/).
-  static const int kClassic[BCE_NBINS] = {12, 10, 11, 9, 8, 7, 6, 5, 4, 3, 2, 1, 0};
-  int kOrder[BCE_NBINS];
-  {
-    int k = 0;
-    for (int pass = 0; pass < 3; ++pass)
-      for (int oi = 0; oi < BCE_NBINS; ++oi) {
-        const int b = kClassic[oi];
-        const bool side = b <= side_last;
-        const bool small = !side && b < BCE_NBINS - 1 && !merged_away[b] && few(lo[b], b);
-        if ((pass == 0 && !side && !small) || (pass == 1 && small) || (pass == 2 && side)) kOrder[k++] = b;
-      }
-  }
-  for (int oi = 0; oi < BCE_NBINS && !rc; ++oi) {
-    const int b = kOrder[oi];
-    if (merged_away[b]) continue;
-    const int b0 = lo[b];
-    ConsArgs a = base;
-    a.list = order + bin_start_host[b0];
-    a.n_list = bin_start_host[b + 1] - bin_start_host[b0];
-    if (b0 != b) {  // merged: this bin's (longer) markets first, then the bins below
-      a.list_hi = order + bin_start_host[b];
-      a.n_hi = bin_start_host[b + 1] - bin_start_host[b];
-    }
-    if (a.n_list == 0) continue;
-    hipStream_t sb = (b <= side_last) ? side : st;
-    if (b <= 3 && seg_ok) {
-      static const int lens[4] = {8, 16, 32, 64};
-      rc = launch_seg_for_len(lens[b], a, sb);
-    } else if (b <= BCE_NBINS - 2) {
-      rc = (b <= 3) ? launch_long_lds(a, sb) : launch_wide_for_len(kBinMax[b], a, sb);
-    } else {
-      // scratch stride from the caller's sizing (bce_consensus_scratch_bytes)
-      const int grid = (int)(a.n_list < kHugeGrid ? a.n_list : kHugeGrid);
-      const int64_t P = scratch_bytes / ((int64_t)grid * 4 * 8);
-      if (P <= kLongMaxLds) {  // not BCE_REQUIRE: the side stream must still be joined
-        set_error("planned: scratch too small for the >4096 bin");
-        rc = BCE_EINVAL;
-        break;
-      }
-      a.scratch = scratch;
-      a.scratch_stride = P;
-      hipLaunchKernelGGL((consensus_long_kernel<false>), dim3(grid), dim3(kLongThreads), 0, st, a);
-      rc = check_launch("consensus_long_kernel<global>");
-    }
-    if (rc) break;
-  }
-  const int rj = side_join(st, nside);  // join even after a failed launch: st must not run ahead
-  if (!rc) rc = rj;
-  return rc;
-}
-
-// The planned launch driven by device bin boundaries (bce_plan_bins_device_async): no host
-// sync between planning and consensus.  Every bin's kernel is launched with its resident grid
-// (its market count is not known on the host) and reads its range of the plan order at entry
-// (dev_range); an empty bin's launch exits at once.  The launch structure is the full batch's:
-// EXACT runs the non-power-of-two bins in the launch of the bin above, FAST gives every bin its
-// own launch (no small-call merges: the counts are on the device), longest bins first, bins
-// 0..3 on the side stream.  Markets longer than 4096 are not computed: they raise the device
-// fault word (a caller with such markets uses the host-synchronised plan).
-extern "C" int bce_consensus_planned_device(const int64_t* offsets, int64_t n_markets, const int32_t* sid,
-                                            const double* prob, int64_t n_signals, const double* relconf,
-                                            const uint32_t* present_bits, int32_t n_sources, const int32_t* order,
-                                            const int64_t* bin_start_dev, int32_t mode, double* consensus,
-                                            double* confidence, double* total_weight, int32_t* n_unique,
-                                            int32_t* err_idx, int32_t* usid, double* weight, double* nweight,
-                                            void* stream) {
-  int rc = check_common(offsets, n_markets, sid, prob, relconf, present_bits, n_sources, consensus,
-                        confidence, total_weight, n_unique);
-  if (rc) return rc;
-  if (n_markets == 0) return BCE_OK;
-  BCE_REQUIRE(bin_start_dev && order, "planned_device: missing plan");
-  BCE_REQUIRE(mode == BCE_MODE_EXACT || mode == BCE_MODE_FAST, "planned_device: bad mode %d", mode);
-  BCE_REQUIRE(n_signals == 0 || (sid && prob), "planned_device: sid/prob NULL");
-  hipStream_t st = as_stream(stream);
-  ConsArgs base{};
-  base.offsets = offsets; base.sid = sid; base.prob = prob;
-  base.relconf = reinterpret_cast<const double2*>(relconf); base.pbits = present_bits;
-  base.n_sources = n_sources; base.n_signals = n_signals; base.consensus = consensus; base.confidence = confidence;
-  base.total_weight = total_weight; base.n_unique = n_unique; base.err_idx = err_idx;
-  base.usid = usid; base.weight = weight; base.nweight = nweight; base.mode = mode;
-  base.fault = fault_word();
-  base.spin_cap = spin_cap();
-  base.list = order;           // the whole plan order: each launch's range is read on the device
-  base.n_list = n_markets;     // upper bound: sizes the launch grids
-  base.dev_bins = bin_start_dev;
-  const bool seg_ok = n_sources <= (1 << 25);
-  hipStream_t side = st;
-  std::unique_lock<std::mutex> fork_lock;
-  rc = side_fork(st, 1, &side, &fork_lock);
-  if (rc) return rc;
-  static const int kOrderDev[BCE_NBINS - 1] = {10, 11, 9, 8, 7, 6, 5, 4, 3, 2, 1, 0};
-  for (int oi = 0; oi < BCE_NBINS - 1 && !rc; ++oi) {
-    const int b = kOrderDev[oi];
-    const bool np2 = (b == kBinNp2Lo || b == kBinNp2Hi);
-    if (mode == BCE_MODE_EXACT && np2) continue;  // rides in the launch of the bin above
-    ConsArgs a = base;
-    a.dev_b1 = b;
-    a.dev_b0 = (mode == BCE_MODE_EXACT && (b == kBinNp2Lo + 1 || b == kBinNp2Hi + 1)) ? b - 1 : b;
-    hipStream_t sb = (b <= kPlanSideLast) ? side : st;
-    if (b <= 3 && seg_ok) {
-      static const int lens[4] = {8, 16, 32, 64};
-      rc = launch_seg_for_len(lens[b], a, sb);
-    } else if (b <= 3) {
-      rc = BCE_EUNSUPPORTED;  // (n_sources > 2^25: the long-LDS kernel has no device range)
-      set_error("planned_device: more than 2^25 sources -- use bce_consensus_planned");
-    } else {
-      rc = launch_wide_for_len(kBinMax[b], a, sb);
-    }
-  }
-  const int rj = side_join(st, 1);
-  if (!rc) rc = rj;
-  return rc;
-}
-
-// ======================================================================================
-// validation only: core.validate_input_payload range check (core.py:59-60)
-// ======================================================================================
-namespace bce {
-__global__ __launch_bounds__(256) void validate_kernel(const int64_t* offsets, int64_t n_markets,
-                                                       const double* prob, int32_t* err_idx) {
-  const int lane = lane_id();
-  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t m = wave; m < n_markets; m += nwaves) {
-    const int64_t a = offsets[m], b = offsets[m + 1];
-    int32_t e = -1;
-    for (int64_t base = a; base < b; base += 64) {
-      const int64_t i = base + lane;
-      const double p = (i < b) ? prob[i] : 0.5;
-      const unsigned long long bad = ballot(p < 0.0 || p > 1.0);  // NaN passes
-      if (bad) {
-        e = (int32_t)(base - a) + __builtin_ctzll(bad);
-        break;
-      }
-    }
-    if (lane == 0) err_idx[m] = e;
-  }
-}
-}  // namespace bce
-
-
-extern "C" int bce_validate_csr(const int64_t* offsets, int64_t n_markets, const double* prob,
-                                int32_t* err_idx, void* stream) {
-  BCE_REQUIRE(n_markets >= 0, "validate: n_markets < 0");
-  if (n_markets == 0) return BCE_OK;
-  BCE_REQUIRE(offsets && prob && err_idx, "validate: NULL argument");
-  int64_t blocks = (n_markets + 3) / 4;
-  const int64_t cap = (int64_t)cu_count() * 16;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(validate_kernel, dim3((int)blocks), dim3(256), 0, as_stream(stream), offsets,
-                     n_markets, prob, err_idx);
-  return check_launch("validate_kernel");
-}
-
-// ======================================================================================
-// source-table packing: separate (rel, conf, present) -> the consensus layout
-// ======================================================================================
-namespace bce {
-__global__ __launch_bounds__(256) void table_pack_kernel(int64_t n, const double* rel, const double* conf,
-                                                         const uint8_t* present, double2* relconf,
-                                                         uint32_t* bits) {
-  const int lane = lane_id();
-  for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < ((n + 63) & ~63ll);
-       s += (int64_t)gridDim.x * blockDim.x) {
-    const bool in = s < n;
-    if (in) relconf[s] = make_double2(rel[s], conf[s]);
-    const unsigned long long b = ballot(in && (present == nullptr || present[s] != 0));
-    if (lane == 0 && s < n) bits[s >> 5] = (uint32_t)b;
-    if (lane == 32 && s < n) bits[s >> 5] = (uint32_t)(b >> 32);
-  }
-}
-}  // namespace bce
-
-extern "C" int bce_table_pack(int64_t n, const double* rel, const double* conf, const uint8_t* present,
-                              double* relconf, uint32_t* present_bits, void* stream) {
-  BCE_REQUIRE(n >= 0, "table_pack: n < 0");
-  if (n == 0) return BCE_OK;
-  BCE_REQUIRE(rel && conf && relconf && present_bits, "table_pack: NULL argument");
-  BCE_REQUIRE((uintptr_t)relconf % 16 == 0, "table_pack: relconf must be 16-byte aligned");
-  int64_t blocks = (n + 255) / 256;
-  const int64_t cap = (int64_t)cu_count() * 16;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(table_pack_kernel, dim3((int)blocks), dim3(256), 0, as_stream(stream), n, rel, conf,
-                     present, reinterpret_cast<double2*>(relconf), present_bits);
-  return check_launch("table_pack_kernel");
-}

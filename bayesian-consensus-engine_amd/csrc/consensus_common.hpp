@@ -1,6 +1,7 @@
 // consensus_common.hpp -- declarations shared by the consensus translation units
-// (consensus.hip: list / long-market kernels, launchers and the C ABI; consensus_tab.hip:
-// the LDS-table kernel for contiguous short markets; consensus_wide.hip: 64 < n <= 4096).
+// (consensus.hip: list / long-market kernels and their launchers; consensus_tab.hip: the
+// LDS-table kernel for contiguous short markets; consensus_wide.hip: 64 < n <= 4096;
+// consensus_api.hip: the C entries that pick among them; plan.hip: the planners).
 #pragma once
 #pragma clang fp contract(off)
 
@@ -187,6 +188,13 @@ constexpr int kTabMaxSources = 10112;  // 16 B per source + the bitmask fit the 
 constexpr int kTabHybMaxSources = 1 << 18;
 constexpr int kTabLdsBytes = 160 * 1024;
 int launch_tab32(const ConsArgs& a, hipStream_t st);
+
+// consensus.hip: markets with n <= max_len <= 64 (n_sources <= 2^25: 32-bit (sid, index) keys);
+// the long kernel sorting in LDS (n <= 4096, any table); and sorting in `scratch`, slices of
+// `stride` keys per workgroup (plan_host.hpp long_scratch_bytes / long_scratch_stride).
+int launch_seg_for_len(int max_len, const ConsArgs& a, hipStream_t st);
+int launch_long_lds(const ConsArgs& a, hipStream_t st);
+int launch_long_global(ConsArgs a, void* scratch, int64_t stride, hipStream_t st);
 
 // Register-sort kernel (consensus_wide.hip) for 64 < n <= 4096: keys (sid << ib) | index with
 // ib = log2 of the bin's padded size (7..12), 32 bits while n_sources <= 2^(32 - ib), else 64.

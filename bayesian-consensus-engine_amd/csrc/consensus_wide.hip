@@ -1093,48 +1093,18 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WideCfg
   }
 }
 
-template <int NW, int R, bool FAST, int NN, class KT>
-int64_t resident_kt() {
-  const void* fn = reinterpret_cast<const void*>(&consensus_wide_kernel<NW, R, FAST, NN, KT>);
-  return (int64_t)cu_count() * blocks_per_cu(fn, 64 * NW, 0, 1, "consensus_wide_kernel");
-}
-
-template <int NW, int R, bool FAST, int NN = NW>
-int64_t resident_wide(int32_t n_sources) {
-  constexpr int IB = WideCfg<NW, R, FAST, NN>::IB;
-  return ((int64_t)n_sources <= (1ll << (32 - IB))) ? resident_kt<NW, R, FAST, NN, unsigned>()
-                                                     : resident_kt<NW, R, FAST, NN, uint64_t>();
-}
-
-template <bool FAST>
-int64_t resident_mode(int64_t max_len, int32_t n_sources) {
-  if (max_len <= 128) return resident_wide<1, 2, FAST>(n_sources);
-  if (max_len <= 256) return resident_wide<1, 4, FAST>(n_sources);
-  if (max_len <= 512) return resident_wide<1, 8, FAST>(n_sources);
-  if (max_len <= 1024) return resident_wide<2, 8, FAST>(n_sources);
-  if (max_len <= 1536) return resident_wide<3, 8, FAST, 4>(n_sources);
-  if (max_len <= 2048) return resident_wide<4, 8, FAST>(n_sources);
-  if (max_len <= 3072) return resident_wide<6, 8, FAST, 8>(n_sources);
-  return resident_wide<8, 8, FAST>(n_sources);
-}
-
-template <int NW, int R, bool FAST, int NN, class KT>
-int launch_wide_kt(const ConsArgs& a, hipStream_t st) {
-  const void* fn = reinterpret_cast<const void*>(&consensus_wide_kernel<NW, R, FAST, NN, KT>);
-  const int per_cu = blocks_per_cu(fn, 64 * NW, 0, 1, "consensus_wide_kernel");
-  const int64_t cap = (int64_t)cu_count() * per_cu;
-  const int grid = (int)(a.n_list < cap ? a.n_list : cap);
-  hipLaunchKernelGGL((consensus_wide_kernel<NW, R, FAST, NN, KT>), dim3(grid), dim3(64 * NW), 0, st, a);
-  return check_launch("consensus_wide_kernel");
-}
+// The kernel of a wide launch and its workgroup size.
+struct WideKernel {
+  void (*fn)(ConsArgs);
+  int threads;
+};
 
 // 32-bit keys while the sid fits beside the IB index bits, 64-bit keys for larger tables
 template <int NW, int R, bool FAST, int NN = NW>
-int launch_wide(const ConsArgs& a, hipStream_t st) {
-  if (a.n_list == 0) return BCE_OK;
+WideKernel wide_kernel(int32_t n_sources) {
   constexpr int IB = WideCfg<NW, R, FAST, NN>::IB;
-  if ((int64_t)a.n_sources <= (1ll << (32 - IB))) return launch_wide_kt<NW, R, FAST, NN, unsigned>(a, st);
-  return launch_wide_kt<NW, R, FAST, NN, uint64_t>(a, st);
+  if ((int64_t)n_sources <= (1ll << (32 - IB))) return {consensus_wide_kernel<NW, R, FAST, NN, unsigned>, 64 * NW};
+  return {consensus_wide_kernel<NW, R, FAST, NN, uint64_t>, 64 * NW};
 }
 
 // (NW, R[, NN]) per length bin: P = 64*NW*R >= max_len; the 1536 and 3072 bins run the
@@ -1143,15 +1113,23 @@ int launch_wide(const ConsArgs& a, hipStream_t st) {
 // latency per market, more rounds -- made one 8th of C3 slower, 0.2069-0.2072 -> 0.2274-0.2300
 // ms, profiles/archive/r05g/; removed.)
 template <bool FAST>
-int launch_wide_mode(int64_t max_len, const ConsArgs& a, hipStream_t st) {
-  if (max_len <= 128) return launch_wide<1, 2, FAST>(a, st);
-  if (max_len <= 256) return launch_wide<1, 4, FAST>(a, st);
-  if (max_len <= 512) return launch_wide<1, 8, FAST>(a, st);
-  if (max_len <= 1024) return launch_wide<2, 8, FAST>(a, st);
-  if (max_len <= 1536) return launch_wide<3, 8, FAST, 4>(a, st);
-  if (max_len <= 2048) return launch_wide<4, 8, FAST>(a, st);
-  if (max_len <= 3072) return launch_wide<6, 8, FAST, 8>(a, st);
-  return launch_wide<8, 8, FAST>(a, st);
+WideKernel wide_kernel_for(int64_t max_len, int32_t n_sources) {
+  if (max_len <= 128) return wide_kernel<1, 2, FAST>(n_sources);
+  if (max_len <= 256) return wide_kernel<1, 4, FAST>(n_sources);
+  if (max_len <= 512) return wide_kernel<1, 8, FAST>(n_sources);
+  if (max_len <= 1024) return wide_kernel<2, 8, FAST>(n_sources);
+  if (max_len <= 1536) return wide_kernel<3, 8, FAST, 4>(n_sources);
+  if (max_len <= 2048) return wide_kernel<4, 8, FAST>(n_sources);
+  if (max_len <= 3072) return wide_kernel<6, 8, FAST, 8>(n_sources);
+  return wide_kernel<8, 8, FAST>(n_sources);
+}
+
+WideKernel wide_kernel_for(int64_t max_len, int32_t mode, int32_t n_sources) {
+  return (mode == BCE_MODE_FAST) ? wide_kernel_for<true>(max_len, n_sources) : wide_kernel_for<false>(max_len, n_sources);
+}
+
+int64_t resident(const WideKernel& k) {
+  return (int64_t)cu_count() * blocks_per_cu(reinterpret_cast<const void*>(k.fn), k.threads, 0, 1, "consensus_wide_kernel");
 }
 
 }  // namespace
@@ -1187,11 +1165,17 @@ extern "C" int bce_debug_lane_selftest(unsigned* out, void* stream) {
 
 
 int64_t wide_resident(int64_t max_len, int32_t mode, int32_t n_sources) {
-  return (mode == BCE_MODE_FAST) ? resident_mode<true>(max_len, n_sources) : resident_mode<false>(max_len, n_sources);
+  return resident(wide_kernel_for(max_len, mode, n_sources));
 }
 
+// One bin per launch: a persistent grid (every workgroup resident) strides over the market list.
 int launch_wide_len(int64_t max_len, const ConsArgs& a, hipStream_t st) {
-  return (a.mode == BCE_MODE_FAST) ? launch_wide_mode<true>(max_len, a, st) : launch_wide_mode<false>(max_len, a, st);
+  if (a.n_list == 0) return BCE_OK;
+  const WideKernel k = wide_kernel_for(max_len, a.mode, a.n_sources);
+  const int64_t cap = resident(k);
+  const int grid = (int)(a.n_list < cap ? a.n_list : cap);
+  hipLaunchKernelGGL(k.fn, dim3(grid), dim3(k.threads), 0, st, a);
+  return check_launch("consensus_wide_kernel");
 }
 
 }  // namespace bce

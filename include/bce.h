@@ -179,6 +179,15 @@ int bce_consensus_planned_device(const int64_t* offsets, int64_t n_markets, cons
                                  int32_t mode, double* consensus, double* confidence, double* total_weight,
                                  int32_t* n_unique, int32_t* err_idx, int32_t* usid, double* weight,
                                  double* nweight, void* stream);
+/* The launches bce_consensus_planned makes for a plan (bin_start_host, host int64[BCE_NBINS+1]),
+ * or bce_consensus_planned_device makes (bin_start_host NULL), in issue order.  Host code only:
+ * no GPU, and the resident workgroups of each wide bin's kernel come from the caller
+ * (resident, host int64[BCE_NBINS], entries 4..11 read) -- a cost model prices a rank's markets
+ * with it (sharding._rank_main_us).  launches: host int32[BCE_NBINS][3], rows {b0, b1, side}:
+ * the markets of bins b0..b1 in one kernel sized for bin b1, side != 0 on the side stream;
+ * *n_launches rows are written.  *fork: whether the side stream is forked and joined. */
+int bce_plan_schedule(const int64_t* bin_start_host, int32_t mode, const int64_t* resident, int32_t* launches,
+                      int32_t* n_launches, int32_t* fork);
 /* Bytes of device scratch bce_consensus_planned needs for the >4096 bin. */
 int64_t bce_consensus_scratch_bytes(const int64_t* offsets_host, const int32_t* order_host,
                                     const int64_t* bin_start_host);

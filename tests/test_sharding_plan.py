@@ -77,6 +77,28 @@ def test_planned_split_is_a_balanced_partition_of_length_classes(world, mode):
         assert all(len([x for x in s if x <= 3]) <= 2 and len([x for x in s if x > 3]) <= 4 for s in bins_of), bins_of
 
 
+# (market count, sum of market indices) of every rank for the batch above, recorded when
+# sharding._rank_main_us still restated the library's merge rules in Python: taking them from
+# bce_plan_schedule must not move a market.
+SPLIT = {
+    ('fast', 2): [(47233, 1381756592), (12767, 418213408)],
+    ('fast', 3): [(41000, 1204270029), (10689, 334853615), (8311, 260846356)],
+    ('fast', 8): [(25783, 675295094), (11623, 415711186), (5719, 197407554), (4234, 97019896), (3293, 108401079),
+                  (3231, 99407920), (3108, 82685348), (3009, 124041923)],
+    ('exact', 2): [(47777, 1398070524), (12223, 401899476)],
+    ('exact', 3): [(42179, 1238811675), (9779, 308165255), (8042, 252993070)],
+    ('exact', 8): [(26568, 698638182), (11468, 410976708), (5992, 205840871), (3749, 82614763), (3136, 103659974),
+                   (3074, 94819438), (3007, 79483275), (3006, 123936789)],
+}
+
+
+@pytest.mark.parametrize("mode,world", sorted(SPLIT))
+def test_planned_split_is_the_recorded_one(mode, world):
+    off = _offsets(7, M=60000, edges=False)
+    got = [shard_markets_planned(off, world, r, mode=mode) for r in range(world)]
+    assert [(len(mk), int(mk.sum())) for mk in got] == SPLIT[(mode, world)]
+
+
 def test_gather_csr_rebuilds_the_rank_batch():
     off = _offsets(3, M=3000)
     rng = np.random.default_rng(3)

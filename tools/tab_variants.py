@@ -23,9 +23,11 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bayesian-consensus-engine_amd", "csrc")
 OUT = os.path.join(ROOT, "tools", "bin", "variants")  # gitignored; travels to the GPU box
-SRCS = ["capi.hip", "consensus.hip", "consensus_tab.hip", "consensus_wide.hip", "elementwise.hip", "tiebreak.hip",
-        "stats.hip", "aggregate.hip"]
-CPP_SRCS = ["jsonl.cpp"]
+# the translation units of csrc/Makefile (SRCS, CPPSRCS)
+SRCS = ["capi.hip", "consensus.hip", "consensus_api.hip", "consensus_tab.hip", "consensus_wide.hip", "plan.hip",
+        "elementwise.hip", "tiebreak.hip", "stats.hip", "aggregate.hip", "reestimate_csr.hip", "settle.hip",
+        "pair_scope.hip", "glob.hip"]
+CPP_SRCS = ["jsonl.cpp", "errors.cpp"]
 
 _XPOSE_NEW = """  for (int i = 0; i < N; ++i)
     if (!(i & 4)) bfly_r8(r[i], r[i | 4], lane);

@@ -35,8 +35,8 @@ OUT = tab_variants.OUT
 VARIANTS = {
     "wbase": [],
     # small planned calls without the bin merges / merging below 3 resident rounds (shipped: 6)
-    "nomerge": [("consensus.hip", "constexpr double kMergeRounds = 6.0;", "constexpr double kMergeRounds = 0.0;")],
-    "merge3": [("consensus.hip", "constexpr double kMergeRounds = 6.0;", "constexpr double kMergeRounds = 3.0;")],
+    "nomerge": [("plan_host.hpp", "constexpr double kMergeRounds = 6.0;", "constexpr double kMergeRounds = 0.0;")],
+    "merge3": [("plan_host.hpp", "constexpr double kMergeRounds = 6.0;", "constexpr double kMergeRounds = 3.0;")],
     # C2 tab kernel: the next tile's metadata read after the walk (no spill stores in the tile
     # loop; shipped: at the top of the tile, as round 4)
     "tablate": [("consensus_tab.hip", "constexpr bool kTabMetaEarly = true;", "constexpr bool kTabMetaEarly = false;")],
