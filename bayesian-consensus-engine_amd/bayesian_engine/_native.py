@@ -101,6 +101,8 @@ _SIGS = {
                                                                _vp, _vp, _vp, _vp]),
     "bce_pair_resolve": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _i64] + [_vp] * 6 + [_i64, _i32] + [_vp] * 8 +
                          [_i32, _i64, _f64, _f64, _f64, _f64, _i32] + [_vp] * 10),
+    "bce_scope_resolve": (C.c_int, [_vp, _i64, _vp, _vp, _i64] + [_vp] * 6 + [_i64, _vp, _vp, _i64] + [_vp] * 5 +
+                          [_i64, _i32] + [_vp] * 4 + [_i32, _i64, _f64, _f64, _f64, _f64, _i32] + [_vp] * 8),
     "bce_aggregate_groups": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bce_glob_match": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "bce_glob_match_host": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),

@@ -1205,12 +1205,15 @@ class PairConsensusResult:
     scope: torch.Tensor
     matched: torch.Tensor
     lb: torch.Tensor
+    dmatched: Optional[torch.Tensor] = None  # with ``domains=``: the domain row of every entry
+    dlb: Optional[torch.Tensor] = None
 
 
 def consensus_pairs(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, pairs: PairTable, now_us: int, *,
                     plan: Optional[PairPlan] = None, domain: Optional[ScopeTable] = None,
                     global_scope: Optional[ScopeTable] = None, namespaced: bool = False, apply_decay: bool = True,
-                    mark_cold: bool = False, **consensus_kwargs) -> PairConsensusResult:
+                    mark_cold: bool = False, domains: Optional[PairTable] = None,
+                    market_domain: Optional[torch.Tensor] = None, **consensus_kwargs) -> PairConsensusResult:
     """compute_consensus for every CSR market with the reliability of every signal read at
     MARKET scope: one :func:`pair_resolve` launch builds the consensus table over the batch's
     unique pairs, then :func:`consensus` runs unchanged with ``plan.esid`` as the ranks.
@@ -1218,16 +1221,36 @@ def consensus_pairs(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor
     (get_reliability(sid, str(market.id), apply_decay=True), every source present);
     ``namespaced=True`` adds the fallback to ``domain`` / ``global_scope`` / cold start.  A caller
     that reruns the same CSR builds the :class:`PairPlan` once.  ``consensus_kwargs`` go to
-    :func:`consensus` (``plan=`` there is the length-bin :class:`Plan`, passed as ``bins``)."""
+    :func:`consensus` (``plan=`` there is the length-bin :class:`Plan`, passed as ``bins``).
+
+    ``domains=`` / ``market_domain=`` (together, with ``namespaced=True`` and without the dense
+    ``domain=``, else ``ValueError``) give every market a domain of its own: the sparse domain
+    rows as a :class:`PairTable` over the domain index and the domain index of every market
+    (int32[M], -1 = none).  The lookup is then :func:`scope_resolve` and the result carries
+    ``dlb`` / ``dmatched`` as well."""
+    per_market = domains is not None or market_domain is not None
+    if per_market:
+        if domains is None or market_domain is None:
+            raise ValueError("domains= and market_domain= go together")
+        if domain is not None:
+            raise ValueError("domains= (a domain per market) and domain= (one dense domain) exclude each other")
+        if not namespaced:
+            raise ValueError("domains= needs namespaced=True")
     if plan is None:
         plan = PairPlan.build(offsets, sid, prob, pairs.n_sources)
     if plan.n_markets != pairs.n_markets or plan.n_sources != pairs.n_sources:
         raise ValueError("the plan and the pair table describe different batches")
+    if "bins" in consensus_kwargs:
+        consensus_kwargs["plan"] = consensus_kwargs.pop("bins")
+    if per_market:
+        lb, matched, dlb, dmatched, table, scope = scope_resolve(
+            plan.uoffsets, plan.usid, pairs, domains, market_domain, now_us, emarket=plan.emarket,
+            global_scope=global_scope, apply_decay=apply_decay, mark_cold=mark_cold)
+        res = consensus(offsets, plan.esid, prob.to(torch.float64), table, **consensus_kwargs)
+        return PairConsensusResult(res, plan, scope, matched, lb, dmatched, dlb)
     r = pair_resolve(plan.uoffsets, plan.usid, pairs, now_us, mode="namespaced" if namespaced else "store",
                      emarket=plan.emarket, domain=domain, global_scope=global_scope, apply_decay=apply_decay,
                      mark_cold=mark_cold)
-    if "bins" in consensus_kwargs:
-        consensus_kwargs["plan"] = consensus_kwargs.pop("bins")
     res = consensus(offsets, plan.esid, prob.to(torch.float64), r.table, **consensus_kwargs)
     return PairConsensusResult(res, plan, r.scope, r.matched, r.lb)
 
@@ -1291,6 +1314,156 @@ def settle_pairs(plan: PairPlan, pairs: PairTable, offsets: torch.Tensor, prob: 
         out.index_copy_(0, dst_upd, ent[upd])
         new.append(out)
     return PairTable(poffsets, *new, pairs.n_markets, pairs.n_sources), splan
+
+
+# ---------------------------------------------------------------------------------------
+# domain scope per market: a batch whose markets belong to different domains
+# ---------------------------------------------------------------------------------------
+# The rows of the domains are a PairTable with the DOMAIN index in the market's place
+# (SQLiteReliabilityStore.load_pair_table(["__domain__:<d>", ...], names) builds it);
+# ``market_domain`` int32[M] names the domain of every market, -1 = none.
+def scope_resolve(qoffsets: torch.Tensor, qsid: torch.Tensor, pairs: Optional[PairTable], domains: PairTable,
+                  market_domain: torch.Tensor, now_us: int, *, emarket: Optional[torch.Tensor] = None,
+                  global_scope: Optional[ScopeTable] = None, apply_decay: bool = True, mark_cold: bool = False,
+                  index: bool = True, half_life_days: float = DECAY_HALF_LIFE_DAYS,
+                  min_rel: float = DECAY_MINIMUM):
+    """NamespacedReliabilityStore.get_reliability(sid, market_id=m, domain=domain_of(m),
+    apply_decay) for every query entry in one launch (bce_scope_resolve): the pair's market row
+    -> the source's row in the market's domain -> ``global_scope`` -> cold start.  The queries
+    are those of :func:`pair_resolve`; ``pairs=None`` is ``market_id=None``; ``domains`` holds the
+    sparse rows of the D domains, ``market_domain`` int32[M] the domain of every market (-1: none).
+
+    Returns ``(lb, matched, dlb, dmatched, table, scope)``: the market row's lower bound and hit
+    as :func:`pair_resolve` gives them, the same for the domain row (``dlb`` is a row index of
+    ``domains``, 0 for a market without a domain; written whichever scope was chosen), the
+    :class:`SourceTable` over the entry index and the NS_* code of every entry.  ``index=False``
+    skips the four index outputs.  A ``market_domain`` outside ``[-1, D)`` or offsets that are
+    no segments raise the device fault word (``_native.check_faults``)."""
+    L = N.require_gpu()
+    M, Q, S, D = market_domain.numel(), qsid.numel(), domains.n_sources, domains.n_markets
+    if qoffsets.numel() != M + 1:
+        raise ValueError(f"qoffsets must have n_markets + 1 = {M + 1} entries")
+    if pairs is not None and (pairs.n_markets != M or pairs.n_sources != S):
+        raise ValueError("the pair table, the domain table and market_domain describe different batches")
+    if emarket is not None and emarket.numel() != Q:
+        raise ValueError("emarket and qsid differ in length")
+    dev = qoffsets.device
+    assert qoffsets.dtype == torch.int64 and qsid.dtype == torch.int32, "qoffsets int64, qsid int32"
+    assert emarket is None or emarket.dtype == torch.int32, "emarket must be int32"
+    assert market_domain.dtype == torch.int32, "market_domain must be int32"
+    Q1 = max(Q, 1)
+    lb = matched = dlb = dmatched = None
+    if index:
+        lb = torch.empty(Q1, dtype=torch.int64, device=dev)
+        matched = torch.empty(Q1, dtype=torch.uint8, device=dev)
+        dlb = torch.empty(Q1, dtype=torch.int64, device=dev)
+        dmatched = torch.empty(Q1, dtype=torch.uint8, device=dev)
+    relconf = torch.empty((Q1, 2), dtype=torch.float64, device=dev)
+    bits = torch.zeros(max((Q + 31) // 32, 1), dtype=torch.int32, device=dev)
+    scope = torch.empty(Q1, dtype=torch.uint8, device=dev)
+    glob = [None] * 4
+    if global_scope is not None:
+        x = global_scope
+        assert x.rel.numel() == S and x.conf.numel() == S and x.has.numel() == S and x.t_us.numel() == S, \
+            "the global scope must have n_sources rows"
+        glob = (x.rel.to(torch.float64).contiguous(), x.conf.to(torch.float64).contiguous(),
+                x.t_us.to(torch.int64).contiguous(), x.has.to(torch.uint8).contiguous())  # alive until enqueued
+    P = pairs.n_rows if pairs is not None else 0
+    R = domains.n_rows
+    ptab = [N.ptr(t if P else None) for t in ((pairs.psid, pairs.rel, pairs.conf, pairs.t_us, pairs.has)
+                                              if pairs is not None else [None] * 5)]
+    dtab = [N.ptr(t if R else None) for t in (domains.psid, domains.rel, domains.conf, domains.t_us, domains.has)]
+    mdom = market_domain.contiguous()
+    N.check(L.bce_scope_resolve(N.ptr(qoffsets), M, N.ptr(qsid if Q else None), N.ptr(emarket if Q else None), Q,
+                                N.ptr(pairs.poffsets if pairs is not None else None), *ptab, P,
+                                N.ptr(mdom if M else None), N.ptr(domains.poffsets), D, *dtab, R, S,
+                                *[N.ptr(g) for g in glob], int(bool(apply_decay)), int(now_us),
+                                float(half_life_days), float(min_rel), DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE,
+                                int(bool(mark_cold)), N.ptr(lb), N.ptr(matched), N.ptr(dlb), N.ptr(dmatched),
+                                N.ptr(relconf), N.ptr(bits), N.ptr(scope), N.stream(dev)), "bce_scope_resolve")
+    cut = lambda t: None if t is None else t[:Q]  # noqa: E731
+    table = SourceTable(relconf, bits, range(Q))  # "names": the entry indices
+    return cut(lb), cut(matched), cut(dlb), cut(dmatched), table, cut(scope)
+
+
+@dataclass
+class DomainPlan(PairPlan):
+    """A CSR batch compiled over its unique (domain, source) pairs: a :class:`PairPlan` whose
+    "markets" are the D domains.  One entry per pair over the signals of markets with a domain,
+    in (domain, ascending sid) order: ``uoffsets`` int64[D+1], ``usid`` int32[F], ``emarket``
+    int32[F] (the DOMAIN of every entry), ``esid`` int32[N] (every signal's entry index; 0, a
+    valid placeholder, for the signals of markets without a domain), ``n_markets`` = D, and the
+    ``market_domain`` int32[M] it was built from.  The functions that take a :class:`PairPlan`
+    and a :class:`PairTable` take this plan and the domain table."""
+
+    market_domain: Optional[torch.Tensor] = None
+
+    @classmethod
+    def build(cls, offsets: torch.Tensor, sid: torch.Tensor, market_domain: torch.Tensor, n_sources: int,
+              n_domains: int) -> "DomainPlan":
+        """Torch only (any device, CPU included), synchronises.  A ``sid`` outside ``[0,
+        n_sources)``, a ``market_domain`` entry outside ``[-1, n_domains)``, a ``market_domain``
+        of another length than the markets, offsets that do not rise from 0 to ``len(sid)`` or
+        2^31 entries: ``ValueError``."""
+        M, Nsig = offsets.numel() - 1, sid.numel()
+        try:
+            S, D = int(n_sources), int(n_domains)
+        except (TypeError, ValueError):
+            raise ValueError(f"n_sources / n_domains must be integers (got {n_sources!r}, {n_domains!r})") from None
+        if M < 0 or offsets.dim() != 1:
+            raise ValueError("offsets must be a 1-D tensor of n_markets + 1 entries")
+        if M >= (1 << 31):
+            raise ValueError(f"{M} markets (the signal-to-market map is int32)")
+        if not 0 < S < (1 << 31):
+            raise ValueError(f"n_sources must be in [1, 2^31) (got {n_sources})")
+        if not 0 <= D < (1 << 31):
+            raise ValueError(f"n_domains must be in [0, 2^31) (got {n_domains})")
+        if market_domain.dim() != 1 or market_domain.numel() != M:
+            raise ValueError(f"market_domain must have one entry per market ({M}), got {tuple(market_domain.shape)}")
+        dev = offsets.device
+        offsets = offsets.to(torch.int64)
+        lens = offsets[1:] - offsets[:-1]
+        if M and (int(offsets[0]) != 0 or int(offsets[-1]) != Nsig or int(lens.min()) < 0):
+            raise ValueError("offsets must rise from 0 to len(sid)")
+        if M == 0 and Nsig:
+            raise ValueError("offsets must rise from 0 to len(sid)")
+        if Nsig and (int(sid.min()) < 0 or int(sid.max()) >= S):
+            raise ValueError("a sid is outside [0, n_sources)")
+        mdom = market_domain.to(torch.int64)
+        if M and (int(mdom.min()) < -1 or int(mdom.max()) >= D):
+            raise ValueError("a market_domain entry is outside [-1, n_domains)")
+        i64 = dict(dtype=torch.int64, device=dev)
+        dom = torch.repeat_interleave(mdom, lens, output_size=Nsig)  # the domain of every signal
+        idx = torch.nonzero(dom >= 0).flatten()
+        ukey, inv = torch.unique(dom[idx] * S + sid[idx].to(torch.int64), return_inverse=True)  # sorted
+        F = ukey.numel()
+        if F >= (1 << 31):
+            raise ValueError(f"{F} unique (domain, source) pairs (entries are indexed with int32)")
+        edom = torch.div(ukey, S, rounding_mode="floor")
+        uoffsets = torch.zeros(D + 1, **i64)
+        uoffsets[1:] = torch.cumsum(torch.bincount(edom, minlength=D), 0)
+        esid = torch.zeros(Nsig, dtype=torch.int32, device=dev)
+        esid[idx] = inv.to(torch.int32)
+        return cls(uoffsets, (ukey - edom * S).to(torch.int32), edom.to(torch.int32), esid, D, F, S,
+                   market_domain.to(torch.int32))
+
+
+def settle_domains(plan: DomainPlan, domains: PairTable, offsets: torch.Tensor, prob: torch.Tensor,
+                   outcome: torch.Tensor, now_us: int, **settle_kwargs):
+    """``update_reliability(sid, correct, domain=domain_of(market))`` for every signal of every
+    market with ``outcome >= 0`` and a domain (reliability_abstraction.py:211-229).  The chain of
+    a (domain, source) pair is that source's signals over the domain's markets in (market,
+    position) order -- the reference's loop order.
+
+    This is :func:`settle_pairs` over the (domain, source) entry space, and runs through it: the
+    :class:`SettlePlan` keeps the CSR order inside an entry whichever markets its signals come
+    from, the outcome of a market without a domain is masked to -1 (its signals carry the
+    placeholder entry), and the raw lookup, the chains (long ones chunked) and the merge see the
+    D domains where they saw M markets.  Returns ``(new domain table, settle_plan)``."""
+    if plan.market_domain.numel() != outcome.numel():
+        raise ValueError("outcome must have one entry per market of the plan")
+    masked = torch.where(plan.market_domain.to(outcome.device) >= 0, outcome, torch.full_like(outcome, -1))
+    return settle_pairs(plan, domains, offsets, prob, masked, now_us, **settle_kwargs)
 
 
 # ---------------------------------------------------------------------------------------

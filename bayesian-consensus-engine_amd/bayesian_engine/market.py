@@ -36,6 +36,7 @@ from . import batch
 from .config import DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY, SCHEMA_VERSION
 from .core import compute_consensus
 from .reliability import SQLiteReliabilityStore
+from .reliability_abstraction import NamespacedReliabilityStore
 from . import decay as _decay
 from .timeutil import NO_TIMESTAMP, dt_to_us, iso_to_us
 
@@ -182,16 +183,29 @@ class MarketStore:
         return batch.glob_mask(batch.glob_any(bits, rows), len(self._markets)).cpu().numpy()
 
     def compute_all_consensus(self, reliability_store: Optional[SQLiteReliabilityStore] = None, *,
-                              pair_table: bool = False) -> Dict[str, Dict[str, Any]]:
+                              pair_table: bool = False, domain_of=None) -> Dict[str, Dict[str, Any]]:
         """Consensus for all open markets in ONE batched launch (market.py:200-221).
 
         ``pair_table=True`` (with a store) reads the (source, market) rows through
         ``load_pair_table`` and ``batch.consensus_pairs``: chunked SQL, a sparse table in HBM and
-        one lookup launch instead of a query per market and a host loop per pair.  Same dicts."""
+        one lookup launch instead of a query per market and a host loop per pair.  Same dicts.
+
+        ``domain_of`` (a callable ``Market -> Optional[str]``, or ``"category"`` for
+        ``market.id.category``) needs a :class:`NamespacedReliabilityStore` (else ``TypeError``)
+        and reads every source of every market through its fallback chain,
+        ``get_reliability(sid, market_id=str(market.id), domain=domain_of(market),
+        apply_decay=True)``, the markets of all domains in one batch (the pair-table route)."""
+        if domain_of is not None:
+            if not isinstance(reliability_store, NamespacedReliabilityStore):
+                raise TypeError("domain_of= needs a NamespacedReliabilityStore "
+                                f"(got {type(reliability_store).__name__})")
+            domain_of = _domain_fn(domain_of)
         markets = self.list_markets(status=MarketStatus.OPEN)
         busy = [m for m in markets if m.signals]
         computed: Dict[str, Dict[str, Any]] = {}
-        if busy and pair_table and reliability_store is not None:
+        if busy and domain_of is not None:
+            computed = _batched_consensus_pairs(busy, reliability_store, domain_of)
+        elif busy and pair_table and reliability_store is not None:
             computed = _batched_consensus_pairs(busy, reliability_store)
         elif busy:
             computed = _batched_consensus(busy, reliability_store)
@@ -205,6 +219,15 @@ class MarketStore:
                 market.consensus_result = res
                 results[key] = res
         return results
+
+
+def _domain_fn(domain_of):
+    """``domain_of=``: a callable ``Market -> Optional[str]``, or "category" (MarketId.category)."""
+    if domain_of == "category":
+        return lambda market: market.id.category
+    if not callable(domain_of):
+        raise TypeError(f"domain_of must be a callable Market -> Optional[str] or 'category' (got {domain_of!r})")
+    return domain_of
 
 
 def _batched_consensus(markets: List[Market], store: Optional[SQLiteReliabilityStore]) -> Dict[str, Dict[str, Any]]:
@@ -289,10 +312,15 @@ def _batched_consensus(markets: List[Market], store: Optional[SQLiteReliabilityS
     return out
 
 
-def _batched_consensus_pairs(markets: List[Market], store: SQLiteReliabilityStore) -> Dict[str, Dict[str, Any]]:
+def _batched_consensus_pairs(markets: List[Market], store, domain_of=None) -> Dict[str, Dict[str, Any]]:
     """_batched_consensus with a store, through the pair table: sources ranked once over the
     batch, the (source, market) rows loaded by ``load_pair_table`` and looked up on the GPU
-    (``batch.consensus_pairs``, store mode: every sourceId is in the dict, market.py:209-219)."""
+    (``batch.consensus_pairs``, store mode: every sourceId is in the dict, market.py:209-219).
+
+    With ``domain_of`` the store is a NamespacedReliabilityStore and the lookup is its
+    ``get_reliability(sid, market_id=str(market.id), domain=domain_of(market), apply_decay=True)``:
+    the rows of the batch's domains are a second pair table over the domain index and every
+    market carries its domain (``batch.consensus_pairs(domains=, market_domain=)``)."""
     rank = batch.intern(s["sourceId"] for m in markets for s in m.signals)
     names = list(rank)
     offsets = [0]
@@ -309,11 +337,22 @@ def _batched_consensus_pairs(markets: List[Market], store: SQLiteReliabilityStor
     N.require_gpu()
     dev = N.device()
     T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+    namespaced = {}
+    if domain_of is not None:
+        doms = [domain_of(m) for m in markets]
+        drank = {d: i for i, d in enumerate(dict.fromkeys(d for d in doms if d))}
+        namespaced = dict(
+            namespaced=True,
+            domains=store._store.load_pair_table([f"__domain__:{d}" for d in drank], names, device=dev),
+            market_domain=T(np.array([drank[d] if d else -1 for d in doms], np.int32)),
+            global_scope=store._scope(store.GLOBAL_MARKET_ID, names, dev)[0])
+        store = store._store
     pairs = store.load_pair_table([str(m.id) for m in markets], names, device=dev)
     # get_reliability(apply_decay=True) for every pair, "now" read like decay.py:136-137
     now_us = dt_to_us(_decay.datetime.now(timezone.utc))
     pc = batch.consensus_pairs(T(np.array(offsets, np.int64)), T(np.array(sid_list, np.int32)),
-                               T(np.array(prob_list, np.float64)), pairs, now_us, validate=False, check=True)
+                               T(np.array(prob_list, np.float64)), pairs, now_us, validate=False, check=True,
+                               **namespaced)
     res = pc.result
     cons = res.consensus.cpu().numpy()
     confd = res.confidence.cpu().numpy()
@@ -496,7 +535,7 @@ class CrossMarketAggregator:
 
     def settle_resolved(self, store, domain: Optional[str] = None, update_global: bool = False,
                         patterns: Optional[List[str]] = None, dry_run: bool = False, market_scope: bool = False,
-                        device_match: Optional[bool] = None):
+                        device_match: Optional[bool] = None, domain_of=None):
         """Commit every RESOLVED market with an outcome to the reliability store: the markets
         summarize_sources counts over, in the same order (list_markets, the pattern filter, then
         ``outcome is not None``), passed as ``(signals, outcome)`` to
@@ -505,9 +544,19 @@ class CrossMarketAggregator:
         ``market_scope=True`` passes ``str(market.id)`` for every resolved market, so the rows
         keyed by (source, market) are settled instead (``update_reliability(market_id=...)``, what
         the reference's ``report-outcome --market-id`` writes).  Returns the store's summary: the
-        records and the ``total`` / ``correct`` counts per source (per pair at market scope)."""
+        records and the ``total`` / ``correct`` counts per source (per pair at market scope).
+        ``domain_of`` (as in ``compute_all_consensus``; together with ``domain=``, ``ValueError``)
+        settles every market at the scope of its own domain: ``domains=[domain_of(m), ...]``."""
+        if domain_of is not None:
+            if domain is not None:
+                raise ValueError("domain= (one for the batch) and domain_of= (one per market) exclude each other")
+            domain_of = _domain_fn(domain_of)
         markets = self._select(MarketStatus.RESOLVED, patterns, device_match)
         markets = [m for m in markets if m.outcome is not None]
+        if domain_of is not None:
+            return store.settle_markets([(m.signals, m.outcome) for m in markets], update_global=update_global,
+                                        dry_run=dry_run, domains=[domain_of(m) for m in markets],
+                                        market_ids=[str(m.id) for m in markets] if market_scope else None)
         if market_scope:
             return store.settle_markets([(m.signals, m.outcome) for m in markets], domain=domain,
                                         update_global=update_global, dry_run=dry_run,

@@ -21,7 +21,10 @@ Bulk paths for millions of sources:
   of resolved markets (``batch.SettlePlan``) applied to one domain or global scope;
 * :meth:`SQLiteReliabilityStore.load_pair_table` / :meth:`SQLiteReliabilityStore.settle_pairs` --
   the market-scope rows of a batch of markets as a sparse HBM table (``batch.PairTable``), and
-  the same settlement at market scope, where every (source, market) pair has a row of its own.
+  the same settlement at market scope, where every (source, market) pair has a row of its own;
+* :meth:`SQLiteReliabilityStore.settle_domains` -- that settlement one scope up, for a batch whose
+  markets belong to different domains: the ``__domain__:<d>`` rows are a ``batch.PairTable`` over
+  the domain index and every market names its domain.
 """
 from __future__ import annotations
 
@@ -330,6 +333,51 @@ class SQLiteReliabilityStore:
                 self._conn.execute("BEGIN")
                 self._conn.executemany(_UPSERT_SQL, [(r_.source_id, r_.market_id, r_.reliability, r_.confidence,
                                                       stamp) for r_ in out.values()])
+        return out
+
+    def settle_domains(self, domain_keys: Sequence[str], names: Sequence[str], offsets, sid, prob, outcome,
+                       market_domain, dry_run: bool = False,
+                       now: Optional[datetime] = None) -> Dict[tuple, ReliabilityRecord]:
+        """:meth:`settle_pairs` one scope up, for a batch whose markets belong to different
+        domains: ``update_reliability(source, domain_keys[market_domain[m]], correct)`` for every
+        signal of every market ``m`` with ``outcome >= 0`` and ``market_domain[m] >= 0``, in the
+        reference's loop order.  ``domain_keys`` are the scope keys as stored (``__domain__:<d>``,
+        distinct); their rows come from :meth:`load_pair_table` with the domain index in the
+        market's place, :func:`batch.settle_domains` applies the chains, and the touched (source,
+        domain key) rows are written by one ``executemany`` in a single transaction (``dry_run``:
+        no write).  Returns ``{(source_id, domain_key): record}`` of the touched pairs."""
+        N.require_gpu()
+        dev = N.device()
+        domain_keys = [str(k) for k in domain_keys]
+        names = list(names)
+        T = lambda a, dt: torch.as_tensor(np.asarray(a) if not isinstance(a, torch.Tensor) else a).to(dev, dt)  # noqa: E731
+        offsets, sid = T(offsets, torch.int64), T(sid, torch.int32)
+        prob, outcome = T(prob, torch.float64), T(outcome, torch.int8)
+        market_domain = T(market_domain, torch.int32)
+        domains = self.load_pair_table(domain_keys, names, device=dev)
+        plan = batch.DomainPlan.build(offsets, sid, market_domain, domains.n_sources, len(domain_keys))
+        now_us = dt_to_us(now or datetime.now(timezone.utc))
+        settled, splan = batch.settle_domains(plan, domains, offsets, prob, outcome, now_us)
+        F = plan.n_entries
+        out: Dict[tuple, ReliabilityRecord] = {}
+        if F:
+            # every touched pair now has a row: read them back per entry
+            r = batch.pair_resolve(plan.uoffsets, plan.usid, settled, now_us, mode="raw", emarket=plan.emarket)
+            touched = torch.nonzero(splan.total[:F] > 0).flatten()
+            ed = plan.emarket[touched].cpu().numpy()
+            us = plan.usid[touched].cpu().numpy()
+            rel = r.rel[touched].cpu().numpy()
+            conf = r.conf[touched].cpu().numpy()
+            N.check_faults(dev, "settle_domains")
+            stamp = us_to_iso(now_us)
+            out = {(names[int(s)], domain_keys[int(d)]): ReliabilityRecord(names[int(s)], domain_keys[int(d)],
+                                                                           float(x), float(c), stamp)
+                   for d, s, x, c in zip(ed, us, rel, conf)}
+        if not dry_run and out:
+            with self._conn:  # one transaction
+                self._conn.execute("BEGIN")
+                self._conn.executemany(_UPSERT_SQL, [(r_.source_id, r_.market_id, r_.reliability, r_.confidence,
+                                                      r_.updated_at) for r_ in out.values()])
         return out
 
     def fetch_pairs(self, pairs: Sequence[tuple]) -> Dict[tuple, tuple]:

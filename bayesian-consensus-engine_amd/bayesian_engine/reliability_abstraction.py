@@ -206,7 +206,8 @@ class NamespacedReliabilityStore:
 
     def settle_markets(self, markets: Sequence[tuple], domain: Optional[str] = None, update_global: bool = False,
                        dry_run: bool = False, now: Optional[datetime] = None,
-                       market_ids: Optional[Sequence[str]] = None) -> "SettleSummary":
+                       market_ids: Optional[Sequence[str]] = None,
+                       domains: Optional[Sequence[Optional[str]]] = None) -> "SettleSummary":
         """``update_reliability(sid, correct, domain=domain, update_global=update_global)`` for
         every signal of every resolved market, in list order, as ONE compiled batch.
 
@@ -224,8 +225,25 @@ class NamespacedReliabilityStore:
         market) pair has a row of its own and its chain is that market's signals of the source
         (:meth:`SQLiteReliabilityStore.settle_pairs`).  The summary's ``records`` / ``total`` /
         ``correct`` are then keyed by ``(source_id, market_id)``; with ``update_global`` the
-        source-scope plan also settles ``__global__``."""
+        source-scope plan also settles ``__global__``.
+
+        ``domains`` (one entry per market, falsy = no domain; together with ``domain=``,
+        ``ValueError``; ignored with ``market_ids``, as ``domain`` is) gives every market a domain
+        of its own: per signal ``update_reliability(sid, correct, domain=domains[i],
+        update_global=update_global)``.  A market with a domain settles ``__domain__:<d>``
+        (:meth:`SQLiteReliabilityStore.settle_domains`, distinct domains interned in first-seen
+        order), one without settles ``__global__`` directly, and with ``update_global`` every
+        resolved signal reaches ``__global__`` exactly once (:211-229).  ``records`` / ``total`` /
+        ``correct`` are keyed ``(source_id, domain)``, ``domain`` None for the signals of markets
+        without one (their record is the final ``__global__`` row); ``global_records`` has every
+        source whose global row was written."""
         markets = [(list(signals), outcome) for signals, outcome in markets]
+        if domains is not None:
+            if domain is not None:
+                raise ValueError("domain= (one for the batch) and domains= (one per market) exclude each other")
+            domains = list(domains)
+            if len(domains) != len(markets):
+                raise ValueError(f"domains has {len(domains)} entries for {len(markets)} markets")
         if market_ids is not None:
             market_ids = list(market_ids)
             if len(market_ids) != len(markets):
@@ -258,6 +276,11 @@ class NamespacedReliabilityStore:
         N.require_gpu()
         dev = N.device()
         T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        if domains is not None and market_ids is None:
+            return self._settle_per_domain(markets, domains, names, np.array(offsets, np.int64),
+                                           np.array(sid_list, np.int32), np.array(prob_list, np.float64),
+                                           np.array(outcome_list, np.int8), update_global, dry_run,
+                                           now or datetime.now(timezone.utc))
         plan = batch.SettlePlan.build(T(np.array(offsets, np.int64)), T(np.array(sid_list, np.int32)),
                                       T(np.array(prob_list, np.float64)), T(np.array(outcome_list, np.int8)),
                                       len(names))
@@ -298,6 +321,48 @@ class NamespacedReliabilityStore:
         correct = plan.correct.cpu().numpy()
         return SettleSummary(records, global_records, {sid: int(total[rank[sid]]) for sid in records},
                              {sid: int(correct[rank[sid]]) for sid in records})
+
+    def _settle_per_domain(self, markets, domains, names, offsets, sid, prob, outcome, update_global,
+                           dry_run, now) -> "SettleSummary":
+        """settle_markets(domains=...): the domain rows through settle_domains, then ONE global
+        chain per source -- the signals of the markets without a domain, or with ``update_global``
+        every resolved signal (no second global update where the target already is global,
+        reliability_abstraction.py:225-229) -- through the existing settle."""
+        dnames = list(dict.fromkeys(d for d in domains if d))
+        drank = {d: i for i, d in enumerate(dnames)}
+        market_domain = np.array([drank[d] if d else -1 for d in domains], np.int32)
+        dev = N.device()
+        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        records = {}
+        if dnames:
+            of_key = {f"__domain__:{d}": d for d in dnames}
+            precs = self._store.settle_domains(list(of_key), names, offsets, sid, prob, outcome, market_domain,
+                                               dry_run=dry_run, now=now)
+            for (s, key), r in precs.items():
+                d = of_key[key]
+                records[(s, d)] = NamespacedReliabilityRecord(s, ReliabilityNamespace.DOMAIN, d, r.reliability,
+                                                              r.confidence, r.updated_at, False)
+        gout = outcome if update_global else np.where(market_domain < 0, outcome, np.int8(-1)).astype(np.int8)
+        global_records = {}
+        if bool((gout >= 0).any()):
+            gplan = batch.SettlePlan.build(T(offsets), T(sid), T(prob), T(gout), len(names))
+            grecs = self._store.settle(self.GLOBAL_MARKET_ID, names, gplan, dry_run=dry_run, now=now)
+            global_records = {s: NamespacedReliabilityRecord(s, ReliabilityNamespace.GLOBAL, "global", r.reliability,
+                                                             r.confidence, r.updated_at, False)
+                              for s, r in grecs.items()}
+        total: dict = {}
+        correct: dict = {}
+        for d, (signals, out) in zip(domains, markets):
+            if out is None:
+                continue
+            for s in signals:
+                k = (s["sourceId"], d if d else None)
+                total[k] = total.get(k, 0) + 1
+                correct[k] = correct.get(k, 0) + int((s.get("probability", 0.5) >= 0.5) == bool(out))
+        for k in total:
+            if k[1] is None:
+                records[k] = global_records[k[0]]
+        return SettleSummary(records, global_records, total, correct)
 
     def get_reliability_many(self, names: Sequence[str], market_id: Optional[str] = None,
                              domain: Optional[str] = None, apply_decay: bool = True,

@@ -477,6 +477,42 @@ int bce_pair_resolve(int32_t mode, const int64_t* qoffsets, int64_t n_markets, c
                      uint8_t* scope, double* out_rel, double* out_conf, int64_t* out_t_us, uint8_t* out_present,
                      void* stream);
 
+/* ---- domain scope per market: the namespaced lookup of a batch that spans many domains ------
+ * Replaces, for every unique (market, source) pair of a batch, one call of
+ *   NamespacedReliabilityStore.get_reliability(sid, market_id=m, domain=domain_of(m), apply_decay)
+ * (reliability_abstraction.py:119-188) where the domain differs from market to market;
+ * bce_pair_resolve's BCE_PAIR_NAMESPACED takes one dense domain for the whole call.
+ * Queries and the market table are those of bce_pair_resolve.  The domain rows are sparse and have
+ * the market table's layout with the domain index in the market's place: doffsets[n_domains + 1],
+ * dsid[n_drows] (source ranks, strictly ascending inside a domain), drel / dconf / dt_us / dhas.
+ * market_domain[n_markets] is the domain index of every market, -1 = the market has no domain (a
+ * falsy domain, :150).  Per entry e of market m, in order:
+ *   1. the market row (binary search of qsid[e] in the market's segment) where it exists and phas;
+ *   2. else, if d = market_domain[m] >= 0, the row of the sid in domain d's segment where it
+ *      exists and dhas;
+ *   3. else the dense global row grel.. [n_sources] where ghas (NULL grel skips the scope);
+ *   4. else (default_rel, default_conf).
+ * The chosen row is decayed by its own t_us when apply_decay.  Outputs, all nullable: lb / matched
+ * (the market row, as bce_pair_resolve; 0 / 0 without a market table), dlb[e] = the lower bound of
+ * the sid in the domain's segment (a global row index in [doffsets[d], doffsets[d + 1]]; 0 without
+ * a domain) and dmatched[e], both written whether or not step 2 was reached; relconf, present_bits
+ * (mark_cold), scope (0 / 1 / 2 / 3) as bce_pair_resolve.  poffsets == NULL (with n_rows == 0)
+ * means no market scope: get_reliability(sid, market_id=None, domain=d).
+ * No input makes the kernel read outside its arrays: a qsid outside [0, n_sources) is clamped and
+ * raises the device fault word; so do query / market / domain offsets that decrease or leave their
+ * array (such a segment is searched as empty) and a market_domain entry outside [-1, n_domains)
+ * (the market is treated as having no domain) (bce_fault_check). */
+int bce_scope_resolve(const int64_t* qoffsets, int64_t n_markets, const int32_t* qsid, const int32_t* emarket,
+                      int64_t n_queries, const int64_t* poffsets, const int32_t* psid, const double* prel,
+                      const double* pconf, const int64_t* pt_us, const uint8_t* phas, int64_t n_rows,
+                      const int32_t* market_domain, const int64_t* doffsets, int64_t n_domains,
+                      const int32_t* dsid, const double* drel, const double* dconf, const int64_t* dt_us,
+                      const uint8_t* dhas, int64_t n_drows, int32_t n_sources, const double* grel,
+                      const double* gconf, const int64_t* gt_us, const uint8_t* ghas, int apply_decay,
+                      int64_t now_us, double half_life_days, double min_rel, double default_rel,
+                      double default_conf, int mark_cold, int64_t* lb, uint8_t* matched, int64_t* dlb,
+                      uint8_t* dmatched, double* relconf, uint32_t* present_bits, uint8_t* scope, void* stream);
+
 /* ---- market-id glob patterns: MarketId.matches for every (pattern, market) pair ------
  *
  * Replaces, for a batch: MarketId.matches (market.py:74-82) under MarketStore.list_markets(
