@@ -97,6 +97,10 @@ _SIGS = {
     "bce_settle_compile": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     "bce_settle_apply": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp,
                                    _i64, _f64, _f64, _vp, _vp]),
+    "bce_settle_trace": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _f64,
+                                   _f64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "bce_walk_read": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _f64, _f64, _f64,
+                                _f64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "bce_namespace_resolve": (C.c_int, [_i64] + [_vp] * 12 + [_i32, _i64, _f64, _f64, _f64, _f64, _i32,
                                                                _vp, _vp, _vp, _vp]),
     "bce_pair_resolve": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _i64] + [_vp] * 6 + [_i64, _i32] + [_vp] * 8 +

@@ -131,6 +131,10 @@ class ReliabilityTable:
         """:func:`settle` in place on this table (a domain or the global scope)."""
         settle(plan, self.rel, self.conf, self.t_us, self.present, now_us, **kw)
 
+    def walk_forward(self, plan: "WalkPlan", market_time_us: torch.Tensor, **kw) -> "WalkResult":
+        """:func:`walk_forward` on this table (a domain or the global scope)."""
+        return walk_forward(plan, self, market_time_us, **kw)
+
 
 # ---------------------------------------------------------------------------------------
 # consensus
@@ -1314,6 +1318,217 @@ def settle_pairs(plan: PairPlan, pairs: PairTable, offsets: torch.Tensor, prob: 
         out.index_copy_(0, dst_upd, ent[upd])
         new.append(out)
     return PairTable(poffsets, *new, pairs.n_markets, pairs.n_sources), splan
+
+
+# ---------------------------------------------------------------------------------------
+# walk-forward consensus: every market reads the table as of its turn
+# ---------------------------------------------------------------------------------------
+# Chains of at least WALK_LONG_MIN bits are traced one worker per WALK_CHUNK_BITS bits.
+WALK_LONG_MIN = SETTLE_LONG_MIN
+WALK_CHUNK_BITS = SETTLE_CHUNK_BITS
+
+
+def _walk_queries(pairs: PairPlan, offsets: torch.Tensor, outcome: torch.Tensor):
+    """The integer half of :meth:`WalkPlan.build` behind the entry list (torch only, any device):
+    ``(qstart, qpos, qentry, qlast, slast)``.  An entry of a resolved market contributes as many
+    chain bits as it has signals; the queries are the entries in (source, market) order, ``qpos``
+    the bits of the source before the entry's market, ``qlast`` (by ENTRY) the market of the last
+    of those bits and ``slast`` (by source) the source's last resolved market, -1 where none."""
+    E, S, M = pairs.n_entries, pairs.n_sources, pairs.n_markets
+    dev = offsets.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    usid = pairs.usid[:E].to(torch.int64)
+    emarket = pairs.emarket[:E].to(torch.int64)
+    cnt = torch.bincount(pairs.esid.to(torch.int64), minlength=E)[:E] if E else torch.zeros(0, **i64)
+    cnt = cnt * (outcome[emarket] >= 0)
+    skey, qentry = torch.sort(usid, stable=True)  # entries ascend by market: (source, market) order
+    qstart = torch.zeros(S + 1, **i64)
+    qstart[1:] = torch.cumsum(torch.bincount(usid, minlength=S), 0)
+    c = cnt[qentry]
+    excl = torch.cumsum(c, 0) - c
+    first = qstart[skey]                       # the source's first query
+    qpos = excl - excl[first] if E else excl
+    # the last query before this one, in the same source, whose market left bits
+    at = torch.where(c > 0, torch.arange(E, **i64), torch.full((E,), -1, **i64))
+    incl = torch.cummax(at, 0).values if E else at
+    prev = torch.cat([torch.full((1,), -1, **i64), incl[:-1]]) if E else incl
+    has = prev >= first
+    qm = emarket[qentry]
+    qlast = torch.full((E,), -1, dtype=torch.int32, device=dev)
+    qlast[qentry] = torch.where(has, qm[prev.clamp(min=0)], torch.full((E,), -1, **i64)).to(torch.int32)
+    slast = torch.full((S,), -1, **i64)
+    live = torch.nonzero(qstart[1:] > qstart[:-1]).flatten()
+    if live.numel():
+        end = incl[qstart[1:][live] - 1]
+        ok = end >= qstart[:-1][live]
+        slast[live[ok]] = qm[end[ok]]
+    return qstart, qpos.contiguous(), qentry.to(torch.int32).contiguous(), qlast, slast
+
+
+@dataclass
+class WalkPlan:
+    """A chronological CSR batch compiled for :func:`walk_forward`: the :class:`SettlePlan` of its
+    resolved markets, the :class:`PairPlan` entry list over ALL markets, and one query per entry,
+    regrouped by source: ``qstart`` int64[S+1], ``qpos`` int64[E] (query order, ascending inside a
+    source: the chain position whose before-state the query reads, 0 <= qpos <= chain length),
+    ``qentry`` int32[E] (the entry a query answers), ``qlast`` int32[E] (by entry: the market of
+    chain bit ``qpos - 1``, -1 when ``qpos == 0``) and ``slast`` int64[S] (the last resolved
+    market of every source, -1 where none).  ``n_clamped``: sids outside ``[0, n_sources)``."""
+
+    settle: SettlePlan
+    pairs: PairPlan
+    qstart: torch.Tensor
+    qpos: torch.Tensor
+    qentry: torch.Tensor
+    qlast: torch.Tensor
+    slast: torch.Tensor
+    n_clamped: int
+
+    @property
+    def total(self) -> torch.Tensor:
+        return self.settle.total
+
+    @property
+    def correct(self) -> torch.Tensor:
+        return self.settle.correct
+
+    @classmethod
+    def order(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
+              n_sources: int):
+        """The integer half of :meth:`build` (torch only, CPU tensors included): ``(pairs, qstart,
+        qpos, qentry, qlast, slast, n_clamped)``.  Argument errors as :meth:`SettlePlan.build`."""
+        M = offsets.numel() - 1
+        try:
+            S = int(n_sources)
+        except (TypeError, ValueError):
+            raise ValueError(f"n_sources must be in [1, 2^31) (got {n_sources!r})") from None
+        if not 0 < S < (1 << 31):
+            raise ValueError(f"n_sources must be in [1, 2^31) (got {n_sources})")
+        if outcome.dtype != torch.int8:
+            raise ValueError(f"outcome must be int8 (-1 unresolved, 0, 1), got {outcome.dtype}")
+        if outcome.dim() != 1 or outcome.numel() != M:
+            raise ValueError(f"outcome must have one entry per market ({M}), got {tuple(outcome.shape)}")
+        clamped = sid.to(torch.int32).clamp(0, S - 1)
+        n_clamped = int((clamped != sid).sum())
+        pairs = PairPlan.build(offsets, clamped, prob, S)  # checks offsets / prob
+        return (pairs, *_walk_queries(pairs, offsets, outcome), n_clamped)
+
+    @classmethod
+    def build(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
+              n_sources: int, check: bool = True) -> "WalkPlan":
+        """Compile ``(offsets, sid, prob)`` in chronological market order with ``outcome``
+        int8[M] (-1 unresolved, 0, 1).  Torch sorts and scans plus :meth:`SettlePlan.build`;
+        synchronises.  A ``sid`` outside ``[0, n_sources)`` is clamped and raises
+        :class:`BCEError` (``check=False``: the fault is left for :func:`walk_forward`)."""
+        pairs, qstart, qpos, qentry, qlast, slast, n_clamped = cls.order(offsets, sid, prob, outcome, n_sources)
+        splan = SettlePlan.build(offsets, sid, prob, outcome, n_sources, check=check)
+        if check and n_clamped:  # in an unresolved market: the settlement compile does not see it
+            raise N.BCEError(f"walk plan: {n_clamped} sid outside [0, {int(n_sources)})")
+        return cls(splan, pairs, qstart, qpos, qentry, qlast, slast, n_clamped)
+
+
+@dataclass
+class WalkResult:
+    """:func:`walk_forward`: ``result`` is the batch's :class:`ConsensusResult`, its ``usid``
+    holding the ENTRY index (| cold << 31) as in :class:`PairConsensusResult`; ``scope_present``
+    u8[E]: a row existed when the entry was read; ``total`` / ``correct`` int64[S] of the plan."""
+
+    result: ConsensusResult
+    plan: WalkPlan
+    scope_present: torch.Tensor
+    total: torch.Tensor
+    correct: torch.Tensor
+
+    def __getattr__(self, name):  # the ConsensusResult fields, directly
+        if name in ConsensusResult.__dataclass_fields__:
+            res = self.__dict__.get("result")
+            if res is not None:
+                return getattr(res, name)
+        raise AttributeError(name)
+
+    def is_null(self, offsets: torch.Tensor) -> torch.Tensor:
+        return self.result.is_null(offsets)
+
+
+def walk_trace(plan: WalkPlan, table: "ReliabilityTable", market_time_us: torch.Tensor, *,
+               all_present: bool = True, long_min: Optional[int] = None, chunk_bits: Optional[int] = None,
+               half_life_days: float = DECAY_HALF_LIFE_DAYS, min_rel: float = DECAY_MINIMUM):
+    """The read side of :func:`walk_forward` alone (bce_settle_trace + bce_walk_read): the
+    consensus table over the entry index -- every entry's ``get_reliability(apply_decay=True)`` at
+    its market's time, after the earlier markets were settled -- and ``scope_present`` u8[E].
+    The table is not written."""
+    L = N.require_gpu()
+    sp, pp = plan.settle, plan.pairs
+    S, E, M = sp.n_sources, pp.n_entries, pp.n_markets
+    assert table.rel.dtype == torch.float64 and table.conf.dtype == torch.float64 and \
+        table.t_us.dtype == torch.int64, "rel / conf must be fp64 and t_us int64"
+    assert table.rel.numel() == S and table.conf.numel() == S and table.t_us.numel() == S, \
+        "the table must have n_sources rows"
+    assert table.present is None or (table.present.dtype == torch.uint8 and table.present.numel() == S), \
+        "present must be u8[n_sources]"
+    if market_time_us.dtype != torch.int64 or market_time_us.dim() != 1 or market_time_us.numel() != M:
+        raise ValueError(f"market_time_us must be int64 with one entry per market ({M})")
+    long_min = WALK_LONG_MIN if long_min is None else long_min
+    chunk_bits = WALK_CHUNK_BITS if chunk_bits is None else chunk_bits
+    n_long, chunk_start, n_chunks = sp.chunks(long_min, chunk_bits)
+    dev = table.rel.device
+    st = N.stream(dev)
+    E1 = max(E, 1)
+    relconf = torch.empty((E1, 2), dtype=torch.float64, device=dev)  # the trace, decayed in place
+    bits = torch.zeros(max((E + 31) // 32, 1), dtype=torch.int32, device=dev)
+    exists = torch.empty(E1, dtype=torch.uint8, device=dev)
+    mtime = market_time_us.contiguous()
+    N.check(L.bce_settle_trace(N.ptr(sp.bits), sp.n_bits, N.ptr(sp.start), N.ptr(sp.order), sp.n_touched, n_long,
+                               N.ptr(chunk_start), n_chunks, int(chunk_bits), S, N.ptr(table.rel),
+                               N.ptr(table.conf), N.ptr(table.present), DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE,
+                               N.ptr(plan.qstart), N.ptr(plan.qpos if E else None),
+                               N.ptr(plan.qentry if E else None), E, N.ptr(relconf), st), "bce_settle_trace")
+    ent = lambda t: N.ptr(t if E else None)  # noqa: E731
+    N.check(L.bce_walk_read(E, ent(pp.usid), ent(pp.emarket), ent(plan.qlast), N.ptr(relconf),
+                            N.ptr(mtime if M else None), M, N.ptr(table.rel), N.ptr(table.conf), N.ptr(table.t_us), N.ptr(table.present), S,
+                            float(half_life_days), float(min_rel), DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE,
+                            int(not all_present), int(plan.n_clamped > 0), N.ptr(relconf), N.ptr(bits),
+                            N.ptr(exists), st), "bce_walk_read")
+    return SourceTable(relconf, bits, range(E)), exists[:E]  # "names": the entry indices
+
+
+def walk_forward(plan: WalkPlan, table: "ReliabilityTable", market_time_us: torch.Tensor, *,
+                 offsets: torch.Tensor, prob: torch.Tensor, all_present: bool = True, mode: str = "exact",
+                 long_min: Optional[int] = None, chunk_bits: Optional[int] = None, commit: bool = True,
+                 **consensus_kwargs) -> WalkResult:
+    """The reference run online over a chronological batch, bit-exact: for m = 0..M-1, market m
+    is scored by compute_consensus with ``get_reliability(s, scope, apply_decay=True)`` of every
+    source read with the clock at ``market_time_us[m]`` (reliability.py:104-140), and then, if
+    ``outcome[m] >= 0``, ``update_reliability`` runs for every signal of m in position order and
+    stamps ``updated_at = market_time_us[m]`` (reliability.py:142-233).  ``table`` is one dense
+    scope (a domain or the global table).  Times need not increase: an equal or earlier time reads
+    undecayed.  ``all_present=False`` sets the cold bit of ``usid`` where no row existed at read
+    time (``present == 0`` in the start table and no earlier update in the batch).
+
+    :func:`walk_trace` builds the consensus table over the entries, :func:`consensus` runs
+    unchanged with ``plan.pairs.esid`` as the ranks (``mode`` and ``consensus_kwargs`` go to it;
+    ``bins=`` is its length-bin :class:`Plan`).  ``commit=True`` also leaves the table settled:
+    :func:`settle`'s ``rel`` / ``conf`` / ``present`` with ``t_us`` the time of each source's last
+    resolved market; ``commit=False`` leaves it untouched.  The result does not depend on
+    ``long_min`` / ``chunk_bits`` (defaults WALK_LONG_MIN / WALK_CHUNK_BITS)."""
+    sp, pp = plan.settle, plan.pairs
+    if offsets.numel() - 1 != pp.n_markets or prob.numel() != pp.esid.numel():
+        raise ValueError("offsets / prob are not the batch the plan was built from")
+    wtable, exists = walk_trace(plan, table, market_time_us, all_present=all_present, long_min=long_min,
+                                chunk_bits=chunk_bits)
+    if "bins" in consensus_kwargs:
+        consensus_kwargs["plan"] = consensus_kwargs.pop("bins")
+    res = consensus(offsets, pp.esid, prob.to(torch.float64), wtable, mode=mode, **consensus_kwargs)
+    if commit and sp.n_touched:
+        kw = {}
+        if long_min is not None:
+            kw["long_min"] = long_min
+        if chunk_bits is not None:
+            kw["chunk_bits"] = chunk_bits
+        settle(sp, table.rel, table.conf, table.t_us, table.present, 0, **kw)
+        touched = sp.order.to(torch.int64)
+        table.t_us.index_copy_(0, touched, market_time_us[plan.slast[touched]])
+    return WalkResult(res, plan, exists, sp.total, sp.correct)
 
 
 # ---------------------------------------------------------------------------------------

@@ -38,7 +38,7 @@ from .core import compute_consensus
 from .reliability import SQLiteReliabilityStore
 from .reliability_abstraction import NamespacedReliabilityStore
 from . import decay as _decay
-from .timeutil import NO_TIMESTAMP, dt_to_us, iso_to_us
+from .timeutil import NO_TIMESTAMP, dt_to_us, iso_to_us, us_to_iso
 
 __all__ = ["MarketId", "MarketStatus", "Market", "MarketStore", "SourcePerformance", "CrossMarketAggregator"]
 
@@ -563,6 +563,35 @@ class CrossMarketAggregator:
                                         market_ids=[str(m.id) for m in markets])
         return store.settle_markets([(m.signals, m.outcome) for m in markets], domain=domain,
                                     update_global=update_global, dry_run=dry_run)
+
+    def walk_forward(self, store, patterns: Optional[List[str]] = None, domain: Optional[str] = None,
+                     dry_run: bool = False, device_match: Optional[bool] = None):
+        """A back-test over the store's history: every market with signals (selected as
+        reestimate_sources selects them), ordered by (time, store position) -- ``resolved_at`` for
+        a RESOLVED market with an outcome, ``created_at`` otherwise -- is scored with the
+        reliabilities as they stood after the markets before it were settled and decayed to its
+        own time, then settled itself if it is resolved; unresolved markets read and commit
+        nothing (``store.walk_forward``, :class:`NamespacedReliabilityStore`).  Returns
+        ``(results, summary)``: the consensus dict of every market keyed by ``str(market.id)``, in
+        walk order, and the store's settle summary."""
+        markets = self._select(None, patterns, device_match, with_signals=True)
+        keyed = []
+        for pos, m in enumerate(markets):
+            resolved = m.status == MarketStatus.RESOLVED and m.outcome is not None
+            stamp = m.resolved_at if resolved and m.resolved_at else m.created_at
+            t = iso_to_us(stamp)
+            if t == NO_TIMESTAMP:
+                raise ValueError(f"market {m.id}: no usable time ({stamp!r})")
+            keyed.append((t, pos, m, resolved))
+        keyed.sort(key=lambda k: k[:2])
+        batch_markets = [(m.signals, m.outcome if resolved else None) for _, _, m, resolved in keyed]
+        results, summary = store.walk_forward(batch_markets, [us_to_iso(t) for t, _, _, _ in keyed], domain=domain,
+                                              dry_run=dry_run)
+        out = {}
+        for (_, _, m, _), r in zip(keyed, results):
+            r["marketId"] = str(m.id)
+            out[str(m.id)] = r
+        return out, summary
 
     def summarize_category(self, category: str) -> Dict[str, Any]:
         markets = self._store.list_markets(pattern=f"{category}:*")

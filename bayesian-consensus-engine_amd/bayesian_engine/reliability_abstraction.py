@@ -23,9 +23,10 @@ import torch
 
 from . import _native as N
 from . import batch
-from .config import DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY
+from .config import DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY, SCHEMA_VERSION
+from .core import _no_signals as core_no_signals
 from .reliability import SQLiteReliabilityStore
-from .timeutil import NO_TIMESTAMP, dt_to_us, iso_to_us
+from .timeutil import NO_TIMESTAMP, dt_to_us, iso_to_us, us_to_iso
 
 __all__ = ["ReliabilityNamespace", "NamespacedReliabilityRecord", "ReliabilityProvider",
            "NamespacedReliabilityStore", "SettleSummary"]
@@ -363,6 +364,93 @@ class NamespacedReliabilityStore:
             if k[1] is None:
                 records[k] = global_records[k[0]]
         return SettleSummary(records, global_records, total, correct)
+
+    def walk_forward(self, markets: Sequence[tuple], times: Sequence, domain: Optional[str] = None,
+                     dry_run: bool = False):
+        """The reference run online over a chronological batch, as ONE compiled batch
+        (:func:`batch.walk_forward`): market i is scored by ``compute_consensus`` with every source
+        fetched by ``get_reliability(sid, scope, apply_decay=True)`` at ``times[i]``, then, if its
+        outcome is not None, ``update_reliability(sid, scope, (probability >= 0.5) == outcome)``
+        runs for every signal and stamps the row with ``times[i]``.  ``markets`` is a sequence of
+        ``(signals, outcome)`` as in :meth:`settle_markets`, ``times`` ISO strings or datetimes
+        (one per market); the scope is ``__domain__:<domain>``, or ``__global__`` without a
+        domain.  The scope is loaded once (``load_table``), the sources interned in sorted()
+        order, and the final rows of the touched sources written back with one ``executemany``
+        unless ``dry_run``.  Returns ``(results, summary)``: one dict per market shaped like
+        ``compute_consensus``'s, and the :class:`SettleSummary` of the settled scope."""
+        markets = [(list(signals), outcome) for signals, outcome in markets]
+        times = list(times)
+        if len(times) != len(markets):
+            raise ValueError(f"times has {len(times)} entries for {len(markets)} markets")
+        t_us = np.array([iso_to_us(t) if isinstance(t, str) else dt_to_us(t) for t in times], np.int64)
+        if (t_us == NO_TIMESTAMP).any():
+            raise ValueError("a market time is empty or unparseable")
+        if domain:
+            namespace, value, target = ReliabilityNamespace.DOMAIN, domain, f"__domain__:{domain}"
+        else:
+            namespace, value, target = ReliabilityNamespace.GLOBAL, "global", self.GLOBAL_MARKET_ID
+        rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
+        names = list(rank)
+        offsets = [0]
+        sid_list: List[int] = []
+        prob_list: List[float] = []
+        for signals, _ in markets:
+            for s in signals:
+                prob = s["probability"]
+                if not isinstance(prob, (int, float)):
+                    0 + prob  # noqa: B018  -- builtin sum()'s TypeError (core.py:116)
+                sid_list.append(rank[s["sourceId"]])
+                prob_list.append(float(prob))
+            offsets.append(len(sid_list))
+        outcome = np.array([-1 if o is None else (1 if o else 0) for _, o in markets], np.int8)
+        if not names:
+            return [core_no_signals() for _ in markets], SettleSummary({}, {}, {}, {})
+        N.require_gpu()
+        dev = N.device()
+        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        off, prob = T(np.array(offsets, np.int64)), T(np.array(prob_list, np.float64))
+        plan = batch.WalkPlan.build(off, T(np.array(sid_list, np.int32)), prob, T(outcome), len(names))
+        table = self._store.load_table(target, names, device=dev)
+        res = table.walk_forward(plan, T(t_us), offsets=off, prob=prob, validate=False)
+        N.check_faults(dev, "walk_forward")
+        cons, confd, tot = (x.cpu().numpy() for x in (res.consensus, res.confidence, res.total_weight))
+        n_unique, usid = res.n_unique.cpu().numpy(), res.usid.cpu().numpy()
+        weight, nweight = res.weight.cpu().numpy(), res.nweight.cpu().numpy()
+        esrc = plan.pairs.usid.cpu().numpy()
+        results = []
+        for m, (signals, _) in enumerate(markets):
+            if not signals:
+                results.append(core_no_signals())
+                continue
+            a, u = offsets[m], int(n_unique[m])
+            ids = [names[esrc[usid[a + j] & 0x7FFFFFFF]] for j in range(u)]
+            null = tot[m] == 0
+            results.append({
+                "schemaVersion": SCHEMA_VERSION,
+                "consensus": None if null else float(cons[m]),
+                "confidence": 0.0 if null else float(confd[m]),
+                "sourceWeights": [{"sourceId": ids[j], "weight": float(weight[a + j]),
+                                   "normalizedWeight": float(nweight[a + j])} for j in range(u)],
+                "normalization": {"totalWeight": float(tot[m]), "sourceCount": u},
+                "diagnostics": {"status": "computed", "sources": len(signals), "uniqueSources": u,
+                                "coldStartSources": []},  # every source was fetched: none is cold
+            })
+        touched = sorted(int(x) for x in plan.settle.order.cpu().numpy())
+        rel, conf, stamp_us = table.rel.cpu().numpy(), table.conf.cpu().numpy(), table.t_us.cpu().numpy()
+        total, correct = plan.total.cpu().numpy(), plan.correct.cpu().numpy()
+        records = {names[i]: NamespacedReliabilityRecord(names[i], namespace, value, float(rel[i]), float(conf[i]),
+                                                         us_to_iso(int(stamp_us[i])), False) for i in touched}
+        if not dry_run and records:
+            with self._store._conn:  # one transaction
+                self._store._conn.execute("BEGIN")
+                self._store._conn.executemany(
+                    "INSERT INTO sources (source_id, market_id, reliability, confidence, updated_at) "
+                    "VALUES (?, ?, ?, ?, ?) ON CONFLICT(source_id, market_id) "
+                    "DO UPDATE SET reliability = excluded.reliability, confidence = excluded.confidence, "
+                    "updated_at = excluded.updated_at",
+                    [(r.source_id, target, r.reliability, r.confidence, r.updated_at) for r in records.values()])
+        return results, SettleSummary(records, {}, {names[i]: int(total[i]) for i in touched},
+                                      {names[i]: int(correct[i]) for i in touched})
 
     def get_reliability_many(self, names: Sequence[str], market_id: Optional[str] = None,
                              domain: Optional[str] = None, apply_decay: bool = True,

@@ -26,12 +26,11 @@
 #include "bce_internal.hpp"
 #include "consensus_common.hpp"
 #include "reliability_update.hpp"
+#include "settle_walk.hpp"
 
 #pragma clang fp contract(off)
 
 namespace bce {
-
-constexpr int kSyncRun = 11;  // equal outcomes in a row that pin the reliability to 1.0 / 0.0
 
 __global__ __launch_bounds__(256) void settle_compile_kernel(
     const int64_t* __restrict__ perm, int64_t Np, const int32_t* __restrict__ key,
@@ -76,84 +75,6 @@ __global__ __launch_bounds__(256) void settle_compile_kernel(
     atomicAdd(&correct[s], 1ull);
   }
   if (code && fault) atomicCAS(fault, 0, code);
-}
-
-struct SettleArgs {
-  const unsigned long long* bits;
-  int64_t n_bits;
-  const int64_t* start;  // [S + 1] bit offset of every source's chain
-  const int32_t* order;  // [T] touched sources, longest chain first
-  int64_t T;
-  int64_t n_long;        // the first n_long sources of `order` take the chunked path
-  int32_t S;
-  double* rel;
-  double* conf;
-  int64_t* t_us;
-  uint8_t* present;      // nullable: every row exists
-  int64_t now_us;
-  double default_rel;
-  double default_conf;
-  double2* snap;         // [n_long] {rel, conf} the long chains start from
-  int* fault;
-};
-
-// The chain of source order[q] as a bit range; false (and the fault word) when the plan is not
-// one: the lane then reads and writes nothing.
-__device__ __forceinline__ bool settle_range(const SettleArgs& a, int64_t q, int32_t& s, int64_t& b0,
-                                             int64_t& b1) {
-  s = a.order[q];
-  if (s < 0 || s >= a.S) {
-    if (a.fault) atomicCAS(a.fault, 0, kFaultSid);
-    return false;
-  }
-  b0 = a.start[s];
-  b1 = a.start[s + 1];
-  if (b0 < 0 || b1 < b0 || b1 > a.n_bits) {
-    if (a.fault) atomicCAS(a.fault, 0, kFaultOffsets);
-    return false;
-  }
-  return b1 > b0;
-}
-
-// n confidence updates from c: the chain stops once a step returns its input bit for bit (from
-// the cold start 0.25 after 331 steps, at 0.9999999999999996) -- every later step is that step.
-__device__ __forceinline__ double settle_conf(double c, int64_t n) {
-  for (int64_t k = 0; k < n; ++k) {
-    double next = c;
-    update_conf(next);
-    if (__double_as_longlong(next) == __double_as_longlong(c)) break;
-    c = next;
-  }
-  return c;
-}
-
-// Chain positions [p0, p1) of the chain that starts at bit b0, word by word (the lane streams its
-// own words).  WALK: every bit is one update_rel on r.  TRACK: run / prev follow the length of the
-// current run of equal bits; the first position that completes kSyncRun equal bits ends the span
-// (its bit already applied) and is returned, else -1.
-template <bool WALK, bool TRACK>
-__device__ __forceinline__ int64_t settle_span(const unsigned long long* __restrict__ bits, int64_t b0, int64_t p0,
-                                               int64_t p1, double& r, int& run, bool& prev) {
-  int64_t g = b0 + p0;
-  const int64_t gend = b0 + p1;
-  while (g < gend) {
-    const int sh = (int)(g & 63);
-    unsigned long long w = bits[g >> 6] >> sh;
-    const int64_t left = gend - g;
-    const int n = left < 64 - sh ? (int)left : 64 - sh;
-    for (int k = 0; k < n; ++k) {
-      const bool bit = (w & 1ull) != 0;
-      w >>= 1;
-      if (WALK) update_rel(r, bit);
-      if (TRACK) {
-        run = (run > 0 && bit == prev) ? run + 1 : 1;
-        prev = bit;
-        if (run >= kSyncRun) return g + k - b0;
-      }
-    }
-    g += n;
-  }
-  return -1;
 }
 
 __global__ __launch_bounds__(64) void settle_chain_kernel(SettleArgs a) {

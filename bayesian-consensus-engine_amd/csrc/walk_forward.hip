@@ -1,0 +1,343 @@
+// walk_forward.hip -- walk-forward consensus: every market of a chronological batch reads the
+// reliability table as it stood after the markets before it were settled.
+//
+// The reference run online is, per market m: get_reliability(s, scope, apply_decay=True) for every
+// source of m with the clock at the market's time (reliability.py:104-140, decay.py:90-145), then
+// compute_consensus, then -- if m is resolved -- update_reliability for every signal of m
+// (reliability.py:142-233), which stamps updated_at with that time.  The state a source is read in
+// at market m is therefore a PREFIX state of its settlement chain (settle.hip): the state after
+// the `qpos` bits that belong to earlier markets.  One query per unique (market, source) pair
+// ("entry"), the queries of a source contiguous and ascending in qpos.
+//
+//   trace_chain_kernel  one lane per short chain of `order`: walks the chain as settle_chain_kernel
+//                       does and stores {rel, conf} -- raw, not decayed -- into trace[qentry] at
+//                       every query position it passes
+//   trace_long_kernel   one lane per chunk of a long chain, the workers of settle_long_kernel.
+//                       Every chain position is walked (WALK) by exactly one worker whose state is
+//                       the true state there: worker 0 from the start row to the first sync point,
+//                       worker j from its sync point (exactly 1.0 / 0.0) to the next.  The worker
+//                       that applies bit k - 1 owns query k and stores it, once; no atomics, no
+//                       communication.  Neither kernel writes the table.
+//   walk_read_kernel    one lane per entry: the read side.  qlast >= 0: the traced state, stamped
+//                       with the time of market qlast; qlast < 0 (no earlier bit, qpos == 0): the
+//                       start row, or the cold defaults where none exists.  Decays to the entry's
+//                       own market time and packs the consensus table over the entry index, the
+//                       present bits from one ballot per wave as pair_resolve_kernel does.
+#include "bce_device.hpp"
+#include "bce_internal.hpp"
+#include "consensus_common.hpp"
+#include "decay_device.hpp"
+#include "reliability_update.hpp"
+#include "settle_walk.hpp"
+
+#pragma clang fp contract(off)
+
+namespace bce {
+
+struct TraceArgs {
+  SettleArgs s;           // the chains and the start table (read only; t_us / now_us / snap unused)
+  const int64_t* qstart;  // [S + 1] query range of every source
+  const int64_t* qpos;    // [E] chain position whose before-state the query reads, ascending per source
+  const int32_t* qentry;  // [E] the entry a query answers
+  int64_t E;
+  double2* trace;         // [E] by entry
+};
+
+// A worker's place in its source's queries, and the confidence chain it advances between them.
+struct TraceCursor {
+  int64_t qi, qe;
+  double c;    // confidence after cn steps
+  int64_t cn;
+};
+
+__device__ __forceinline__ void trace_fault(const TraceArgs& a) {
+  if (a.s.fault) atomicCAS(a.s.fault, 0, kFaultOffsets);
+}
+
+// The queries of source s behind chain position pos (qpos > pos: query pos itself belongs to the
+// worker that applied bit pos - 1, query 0 to walk_read_kernel); false when qstart is not a range.
+__device__ __forceinline__ bool trace_queries(const TraceArgs& a, int32_t s, int64_t pos, TraceCursor& cur) {
+  const int64_t qs = a.qstart[s], qe = a.qstart[s + 1];
+  if (qs < 0 || qe < qs || qe > a.E) {
+    trace_fault(a);
+    return false;
+  }
+  int64_t lo = qs, hi = qe;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (a.qpos[mid] <= pos) lo = mid + 1; else hi = mid;
+  }
+  cur.qi = lo;
+  cur.qe = qe;
+  return true;
+}
+
+// Every query at chain position p: the state after p bits, one 16-byte store each.
+__device__ __forceinline__ void trace_emit(const TraceArgs& a, int64_t p, double r, TraceCursor& cur) {
+  while (cur.qi < cur.qe && a.qpos[cur.qi] == p) {
+    if (cur.cn != p) {
+      cur.c = settle_conf(cur.c, p - cur.cn);
+      cur.cn = p;
+    }
+    const int32_t e = a.qentry[cur.qi];
+    if (e < 0 || e >= a.E) trace_fault(a); else a.trace[e] = make_double2(r, cur.c);
+    ++cur.qi;
+  }
+}
+
+// settle_span<true, TRACK> over [p, pend), cut at the query positions in (p, pend], which are
+// stored on the way.  TRACK: the position whose bit completed a sync run (the walk ends behind it,
+// the query there stored), else -1.
+template <bool TRACK>
+__device__ __forceinline__ int64_t trace_span(const TraceArgs& a, int64_t b0, int64_t p, int64_t pend, double& r,
+                                              int& run, bool& prev, TraceCursor& cur) {
+  while (p < pend) {
+    int64_t stop = pend;
+    if (cur.qi < cur.qe) {
+      const int64_t k = a.qpos[cur.qi];
+      if (k <= p) {  // not ascending, or negative: the query is not answered
+        trace_fault(a);
+        ++cur.qi;
+        continue;
+      }
+      if (k < stop) stop = k;
+    }
+    const int64_t hit = settle_span<true, TRACK>(a.s.bits, b0, p, stop, r, run, prev);
+    if (TRACK && hit >= 0) {
+      trace_emit(a, hit + 1, r, cur);
+      return hit;
+    }
+    p = stop;
+    trace_emit(a, p, r, cur);
+  }
+  return -1;
+}
+
+__device__ __forceinline__ void trace_start_row(const SettleArgs& a, int32_t s, double& r, double& c) {
+  const bool pres = a.present ? a.present[s] != 0 : true;
+  r = pres ? a.rel[s] : a.default_rel;  // reliability.py:133-140 cold start
+  c = pres ? a.conf[s] : a.default_conf;
+}
+
+__global__ __launch_bounds__(64) void trace_chain_kernel(TraceArgs a) {
+  const int64_t q = a.s.n_long + (int64_t)blockIdx.x * 64 + threadIdx.x;  // the long chains: trace_long_kernel
+  if (q >= a.s.T) return;
+  int32_t s;
+  int64_t b0, b1;
+  if (!settle_range(a.s, q, s, b0, b1)) return;
+  double r, c;
+  trace_start_row(a.s, s, r, c);
+  TraceCursor cur{0, 0, c, 0};
+  if (!trace_queries(a, s, 0, cur)) return;
+  int run = 0;
+  bool prev = false;
+  trace_span<false>(a, b0, 0, b1 - b0, r, run, prev, cur);
+  if (cur.qi < cur.qe) trace_fault(a);  // a query behind the chain's end
+}
+
+__global__ __launch_bounds__(64) void trace_long_kernel(TraceArgs a, const int64_t* __restrict__ chunk_start,
+                                                        int64_t n_chunks, int64_t C) {
+  const int64_t wk = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (wk >= n_chunks) return;
+  // the long source this chunk belongs to: the last q with chunk_start[q] <= wk
+  int64_t lo = 0, hi = a.s.n_long;
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (chunk_start[mid] <= wk) lo = mid; else hi = mid;
+  }
+  const int64_t q = lo, j = wk - chunk_start[q];
+  int32_t s;
+  int64_t b0, b1;
+  if (j < 0 || !settle_range(a.s, q, s, b0, b1)) return;
+  const int64_t L = b1 - b0;
+  if (j > (L - 1) / C) return;  // more chunks than the chain has: nothing to do
+  const int64_t home_end = (j + 1) * C < L ? (j + 1) * C : L;
+  double r, c;
+  trace_start_row(a.s, s, r, c);
+  int run = 0;
+  bool prev = false;
+  int64_t pos = j * C;
+  if (j > 0) {  // the first run of kSyncRun equal bits that lies inside the home chunk
+    const int64_t p = settle_span<false, true>(a.s.bits, b0, pos, home_end, r, run, prev);
+    if (p < 0) return;    // none: the worker before walks through this chunk and owns its queries
+    r = prev ? 1.0 : 0.0; // exact whatever came before
+    pos = p + 1;          // bit p was applied by the worker before: query p + 1 is theirs
+  }
+  TraceCursor cur{0, 0, c, 0};
+  if (!trace_queries(a, s, pos, cur)) return;
+  trace_span<false>(a, b0, pos, home_end, r, run, prev, cur);  // the rest of the home chunk
+  for (int64_t cb = home_end; cb < L; cb += C) {  // later chunks, until one has a sync run of its own
+    const int64_t cend = cb + C < L ? cb + C : L;
+    run = 0;  // a run counts from its chunk's first bit
+    if (trace_span<true>(a, b0, cb, cend, r, run, prev, cur) >= 0) return;  // that chunk's worker goes on
+  }
+  if (cur.qi < cur.qe) trace_fault(a);  // the one worker that reaches the chain's end
+}
+
+struct WalkReadArgs {
+  int64_t E;
+  const int32_t* usid;     // [E] source of every entry
+  const int32_t* emarket;  // [E]
+  const int32_t* qlast;    // [E] market of the last bit before the entry, -1: none
+  const double2* trace;    // [E]
+  const int64_t* mtime;    // [M]
+  int64_t M;
+  const double* rel;       // [S] the start table
+  const double* conf;
+  const int64_t* t_us;
+  const uint8_t* present;  // nullable: every row exists
+  int32_t S;
+  DecayConst k;            // now_us is set per entry
+  int mark_cold;
+  int clamped;             // the caller clamped a sid while building the entries
+  double2* relconf;        // [E], may be `trace` itself
+  uint32_t* bits;          // [ceil(E / 32)]
+  uint8_t* exists;         // [E] nullable: a row existed at read time
+  int* fault;
+};
+
+constexpr int kWalkGridCap = 8192;  // workgroups, striding like pair_resolve_kernel
+
+__global__ __launch_bounds__(256) void walk_read_kernel(WalkReadArgs a) {
+  __shared__ unsigned long long sExp[256];  // the exp table in LDS (see replay_step_kernel)
+  sExp[threadIdx.x] = kExpTab[threadIdx.x];
+  __syncthreads();
+  if (a.clamped && a.fault && blockIdx.x == 0 && threadIdx.x == 0) atomicCAS(a.fault, 0, kFaultSid);
+  for (int64_t base = (int64_t)blockIdx.x * 256; base < a.E; base += (int64_t)gridDim.x * 256) {
+    const int64_t e = base + threadIdx.x;
+    const bool in = e < a.E;
+    int code = 0;
+    bool exists = false;
+    if (in) {
+      int64_t m = a.emarket[e];
+      if (m < 0 || m >= a.M) {
+        code = kFaultOffsets;
+        m = m < 0 ? 0 : a.M - 1;
+      }
+      int32_t s = a.usid[e];
+      if (s < 0 || s >= a.S) {
+        code = code ? code : kFaultSid;
+        s = s < 0 ? 0 : a.S - 1;
+      }
+      int64_t ql = a.qlast[e];
+      if (ql < -1 || ql >= a.M) {  // not a market: read as "no earlier bit"
+        code = kFaultOffsets;
+        ql = -1;
+      }
+      double r = a.k.default_rel, c = a.k.default_conf;
+      int64_t t = BCE_NO_TIMESTAMP;
+      if (ql >= 0) {  // settled by an earlier market of the batch: updated_at is that market's time
+        const double2 st = a.trace[e];
+        r = st.x;
+        c = st.y;
+        t = a.mtime[ql];
+        exists = true;
+      } else if (a.present == nullptr || a.present[s]) {
+        r = a.rel[s];
+        c = a.conf[s];
+        t = a.t_us[s];
+        exists = true;
+      }
+      if (exists) {  // reliability.py:114-123; a missing row is the cold start, undecayed
+        DecayConst k = a.k;
+        k.now_us = a.mtime[m];
+        r = decayed(r, t, k, sExp);
+      }
+      a.relconf[e] = make_double2(r, c);
+      if (a.exists) a.exists[e] = exists ? 1 : 0;
+    }
+    const unsigned long long w = __ballot(in && (!a.mark_cold || exists));
+    const int ln = (int)(threadIdx.x & 63);
+    const int64_t w0 = (base + (threadIdx.x & ~63)) >> 5;
+    const int64_t nw = (a.E + 31) >> 5;
+    if (ln < 2 && w0 + ln < nw) a.bits[w0 + ln] = (uint32_t)(w >> (32 * ln));
+    if (code && a.fault) atomicCAS(a.fault, 0, code);
+  }
+}
+
+}  // namespace bce
+
+using namespace bce;
+
+extern "C" int bce_settle_trace(const uint64_t* bits, int64_t n_bits, const int64_t* start, const int32_t* order,
+                                int64_t n_touched, int64_t n_long, const int64_t* chunk_start, int64_t n_chunks,
+                                int64_t chunk_bits, int32_t n_sources, const double* rel, const double* conf,
+                                const uint8_t* present, double default_rel, double default_conf,
+                                const int64_t* qstart, const int64_t* qpos, const int32_t* qentry,
+                                int64_t n_entries, double* trace, void* stream) {
+  BCE_REQUIRE(n_bits >= 0 && n_touched >= 0 && n_sources > 0 && n_touched <= n_sources && n_entries >= 0,
+              "settle_trace: bad shape");
+  BCE_REQUIRE(n_entries < (1ll << 31), "settle_trace: n_entries >= 2^31");
+  BCE_REQUIRE(n_long >= 0 && n_long <= n_touched && n_chunks >= 0, "settle_trace: bad long-chain split");
+  if (n_touched == 0 || n_entries == 0) return BCE_OK;
+  BCE_REQUIRE(bits && start && order && rel && conf, "settle_trace: NULL argument");
+  BCE_REQUIRE(qstart && qpos && qentry && trace, "settle_trace: NULL query argument");
+  BCE_REQUIRE((uintptr_t)trace % 16 == 0, "settle_trace: trace must be 16-byte aligned");
+  if (n_long > 0) {
+    BCE_REQUIRE(chunk_start, "settle_trace: long chains need chunk_start");
+    BCE_REQUIRE(chunk_bits >= 64, "settle_trace: chunk_bits < 64");
+    BCE_REQUIRE(n_chunks >= n_long, "settle_trace: fewer chunks than long chains");
+  }
+  const int64_t blocks = (n_touched - n_long + 63) / 64, lblocks = (n_chunks + 63) / 64;
+  BCE_REQUIRE(blocks < (1ll << 31) && lblocks < (1ll << 31), "settle_trace: grid too large");
+  TraceArgs a{};
+  // the trace kernels only read the table: the shared argument block is settle's, which writes it
+  a.s = SettleArgs{reinterpret_cast<const unsigned long long*>(bits), n_bits, start, order, n_touched, n_long,
+                   n_sources, const_cast<double*>(rel), const_cast<double*>(conf), nullptr,
+                   const_cast<uint8_t*>(present), 0, default_rel, default_conf, nullptr, fault_word()};
+  a.qstart = qstart;
+  a.qpos = qpos;
+  a.qentry = qentry;
+  a.E = n_entries;
+  a.trace = reinterpret_cast<double2*>(trace);
+  if (blocks > 0) {
+    hipLaunchKernelGGL(trace_chain_kernel, dim3((unsigned)blocks), dim3(64), 0, as_stream(stream), a);
+    const int rc = check_launch("trace_chain_kernel");
+    if (rc != BCE_OK) return rc;
+  }
+  if (n_long == 0) return BCE_OK;
+  hipLaunchKernelGGL(trace_long_kernel, dim3((unsigned)lblocks), dim3(64), 0, as_stream(stream), a, chunk_start,
+                     n_chunks, chunk_bits);
+  return check_launch("trace_long_kernel");
+}
+
+extern "C" int bce_walk_read(int64_t n_entries, const int32_t* usid, const int32_t* emarket, const int32_t* qlast,
+                             const double* trace, const int64_t* market_time_us, int64_t n_markets,
+                             const double* rel, const double* conf, const int64_t* t_us, const uint8_t* present,
+                             int32_t n_sources, double half_life_days, double min_rel, double default_rel,
+                             double default_conf, int mark_cold, int sid_clamped, double* relconf,
+                             uint32_t* present_bits, uint8_t* exists, void* stream) {
+  BCE_REQUIRE(n_entries >= 0 && n_markets >= 0 && n_sources > 0, "walk_read: bad shape");
+  BCE_REQUIRE(n_entries < (1ll << 31) && n_markets < (1ll << 31), "walk_read: n_entries or n_markets >= 2^31");
+  BCE_REQUIRE(n_markets > 0 || n_entries == 0, "walk_read: entries without markets");
+  if (n_entries == 0 && !sid_clamped) return BCE_OK;
+  BCE_REQUIRE(n_entries == 0 || (usid && emarket && qlast && trace && market_time_us && rel && conf && t_us),
+              "walk_read: NULL argument");
+  BCE_REQUIRE(n_entries == 0 || (relconf && present_bits), "walk_read: NULL output");
+  BCE_REQUIRE((uintptr_t)relconf % 16 == 0 && (uintptr_t)trace % 16 == 0,
+              "walk_read: trace and relconf must be 16-byte aligned");
+  WalkReadArgs a{};
+  a.E = n_entries;
+  a.usid = usid;
+  a.emarket = emarket;
+  a.qlast = qlast;
+  a.trace = reinterpret_cast<const double2*>(trace);
+  a.mtime = market_time_us;
+  a.M = n_markets;
+  a.rel = rel;
+  a.conf = conf;
+  a.t_us = t_us;
+  a.present = present;
+  a.S = n_sources;
+  a.k = DecayConst{0, half_life_days, min_rel, default_rel, default_conf};
+  a.mark_cold = mark_cold;
+  a.clamped = sid_clamped;
+  a.relconf = reinterpret_cast<double2*>(relconf);
+  a.bits = present_bits;
+  a.exists = exists;
+  a.fault = fault_word();
+  const int64_t g = (n_entries + 255) / 256;
+  hipLaunchKernelGGL(walk_read_kernel, dim3((unsigned)(g < 1 ? 1 : (g < kWalkGridCap ? g : kWalkGridCap))), dim3(256),
+                     0, as_stream(stream), a);
+  return check_launch("walk_read_kernel");
+}

@@ -429,6 +429,46 @@ int bce_settle_apply(const uint64_t* bits, int64_t n_bits, const int64_t* start,
                      uint8_t* present, int64_t now_us, double default_rel, double default_conf, double* snap,
                      void* stream);
 
+/* ---- walk-forward consensus: every market reads the table as of its turn ---------------------
+ * A chronological batch run as the reference runs online: market m reads
+ * get_reliability(s, scope, apply_decay=True) with the clock at market_time_us[m]
+ * (reliability.py:104-140), after the resolved markets before it were settled with
+ * update_reliability, each stamping updated_at with its own time (reliability.py:142-233).  The
+ * state an entry -- a unique (market, source) pair, in (market, ascending sid) order -- reads is
+ * the state of its source's settlement chain after the qpos bits of earlier markets.
+ *
+ * bce_settle_trace: the plan of bce_settle_apply (bits .. chunk_bits; the same workers) plus the
+ * queries regrouped by source: qstart[n_sources + 1], qpos[n_entries] (0 <= qpos <= chain length,
+ * ascending inside a source) and qentry[n_entries] (the entry a query answers).  Every query with
+ * qpos > 0 gets {rel, conf} after qpos updates from the source's row (or the cold defaults), raw,
+ * as one 16-byte store into trace[2 * qentry]; each exactly once, by the worker that applied bit
+ * qpos - 1.  Queries with qpos == 0 are not written (bce_walk_read serves them from the row) and
+ * the table is only read.  A qstart that is no range, a qpos that is not ascending or lies
+ * outside the chain, a qentry outside [0, n_entries) raise the fault word and that query is not
+ * answered.  The result does not depend on n_long / chunk_bits.
+ *
+ * bce_walk_read: per entry, the traced state stamped with market_time_us[qlast] where qlast >= 0
+ * (the market of chain bit qpos - 1), else the row of usid (present nullable: every row exists)
+ * or the cold defaults; a state that exists is decayed to market_time_us[emarket] (decay.py:90-145;
+ * equal or earlier times: no decay).  Writes the consensus table over the entry index: relconf
+ * [2 * n_entries] (16-byte aligned; may be `trace` itself), present_bits[ceil(n_entries / 32)]
+ * (all set, or with mark_cold only where a row existed) and exists[n_entries] (nullable).  A
+ * usid outside [0, n_sources) is clamped, an emarket or qlast outside the batch read as 0 / -1,
+ * and the fault word is raised; sid_clamped != 0 (the caller clamped a sid while building the
+ * entries) raises it as a raw sid does elsewhere. */
+int bce_settle_trace(const uint64_t* bits, int64_t n_bits, const int64_t* start, const int32_t* order,
+                     int64_t n_touched, int64_t n_long, const int64_t* chunk_start, int64_t n_chunks,
+                     int64_t chunk_bits, int32_t n_sources, const double* rel, const double* conf,
+                     const uint8_t* present, double default_rel, double default_conf, const int64_t* qstart,
+                     const int64_t* qpos, const int32_t* qentry, int64_t n_entries, double* trace,
+                     void* stream);
+int bce_walk_read(int64_t n_entries, const int32_t* usid, const int32_t* emarket, const int32_t* qlast,
+                  const double* trace, const int64_t* market_time_us, int64_t n_markets, const double* rel,
+                  const double* conf, const int64_t* t_us, const uint8_t* present, int32_t n_sources,
+                  double half_life_days, double min_rel, double default_rel, double default_conf,
+                  int mark_cold, int sid_clamped, double* relconf, uint32_t* present_bits, uint8_t* exists,
+                  void* stream);
+
 /* ---- market-scope rows: the (source, market) rows of the store, looked up per pair ----------
  * Replaces, for every unique (market, source) pair of a batch, one call of
  *   BCE_PAIR_STORE       SQLiteReliabilityStore.get_reliability(sid, market_id, apply_decay)
