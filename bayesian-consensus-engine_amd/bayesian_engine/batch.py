@@ -32,6 +32,11 @@ def intern(ids: Iterable[str]) -> Dict[str, int]:
     return {s: i for i, s in enumerate(sorted(set(ids)))}
 
 
+def to_device(dev):
+    """``T = to_device(dev)``: ``T(a)`` is the numpy array ``a`` as a tensor on ``dev``."""
+    return lambda a: torch.from_numpy(a).to(dev)
+
+
 @dataclass
 class SourceTable:
     """Dense per-source table resident in HBM, in the consensus kernel's layout.
@@ -1133,6 +1138,59 @@ class PairResolveResult:
 _PAIR_MODES = {"store": N.PAIR_STORE, "namespaced": N.PAIR_NAMESPACED, "raw": N.PAIR_RAW}
 
 
+# What :func:`pair_resolve` and :func:`scope_resolve` share on the host.
+def _check_queries(qoffsets: torch.Tensor, qsid: torch.Tensor, emarket: Optional[torch.Tensor], M: int) -> int:
+    Q = qsid.numel()
+    if qoffsets.numel() != M + 1:
+        raise ValueError(f"qoffsets must have n_markets + 1 = {M + 1} entries")
+    if emarket is not None and emarket.numel() != Q:
+        raise ValueError("emarket and qsid differ in length")
+    assert qoffsets.dtype == torch.int64 and qsid.dtype == torch.int32, "qoffsets int64, qsid int32"
+    assert emarket is None or emarket.dtype == torch.int32, "emarket must be int32"
+    return Q
+
+
+def _entry_outputs(Q: int, dev, index: bool, table: bool = True):
+    """``(lb, matched, relconf, bits, scope)`` over max(Q, 1) entries; None where not asked for."""
+    Q1 = max(Q, 1)
+    lb = torch.empty(Q1, dtype=torch.int64, device=dev) if index else None
+    matched = torch.empty(Q1, dtype=torch.uint8, device=dev) if index else None
+    if not table:
+        return lb, matched, None, None, None
+    return (lb, matched, torch.empty((Q1, 2), dtype=torch.float64, device=dev),
+            torch.zeros(max((Q + 31) // 32, 1), dtype=torch.int32, device=dev),
+            torch.empty(Q1, dtype=torch.uint8, device=dev))
+
+
+def _dense_scope(x: Optional[ScopeTable], S: int, what: str):
+    """A dense scope as the four tensors the launch reads (the caller keeps them alive until it is
+    enqueued) and their pointers; None: NULLs."""
+    if x is None:
+        return None, [N.ptr(None)] * 4
+    assert x.rel.numel() == S and x.conf.numel() == S and x.has.numel() == S and x.t_us.numel() == S, what
+    arrs = (x.rel.to(torch.float64).contiguous(), x.conf.to(torch.float64).contiguous(),
+            x.t_us.to(torch.int64).contiguous(), x.has.to(torch.uint8).contiguous())
+    return arrs, [N.ptr(a) for a in arrs]
+
+
+def _pair_pointers(t: Optional["PairTable"]):
+    """psid / rel / conf / t_us / has of a pair table; no table or no rows: NULLs."""
+    if t is None or not t.n_rows:
+        return [N.ptr(None)] * 5
+    return [N.ptr(a) for a in (t.psid, t.rel, t.conf, t.t_us, t.has)]
+
+
+def _cut(Q: int, *tensors):
+    return [None if t is None else t[:Q] for t in tensors]
+
+
+def _bins_as_plan(consensus_kwargs: dict) -> dict:
+    """``bins=`` of the wrappers that have a ``plan=`` of their own is :func:`consensus`'s ``plan=``."""
+    if "bins" in consensus_kwargs:
+        consensus_kwargs["plan"] = consensus_kwargs.pop("bins")
+    return consensus_kwargs
+
+
 def pair_resolve(qoffsets: torch.Tensor, qsid: torch.Tensor, pairs: PairTable, now_us: int, *,
                  mode: str = "store", emarket: Optional[torch.Tensor] = None,
                  domain: Optional[ScopeTable] = None, global_scope: Optional[ScopeTable] = None,
@@ -1150,51 +1208,27 @@ def pair_resolve(qoffsets: torch.Tensor, qsid: torch.Tensor, pairs: PairTable, n
     :func:`settle` updates.  ``index=False`` skips the ``lb`` / ``matched`` outputs."""
     L = N.require_gpu()
     md = _PAIR_MODES[mode]
-    M, Q, S = pairs.n_markets, qsid.numel(), pairs.n_sources
-    if qoffsets.numel() != M + 1:
-        raise ValueError(f"qoffsets must have n_markets + 1 = {M + 1} entries")
-    if emarket is not None and emarket.numel() != Q:
-        raise ValueError("emarket and qsid differ in length")
+    M, S = pairs.n_markets, pairs.n_sources
     if md != N.PAIR_NAMESPACED and (domain is not None or global_scope is not None):
         raise ValueError("domain / global_scope need mode='namespaced'")
+    Q = _check_queries(qoffsets, qsid, emarket, M)
     dev = qoffsets.device
-    assert qoffsets.dtype == torch.int64 and qsid.dtype == torch.int32, "qoffsets int64, qsid int32"
-    assert emarket is None or emarket.dtype == torch.int32, "emarket must be int32"
-    Q1 = max(Q, 1)
-    lb = torch.empty(Q1, dtype=torch.int64, device=dev) if index else None
-    matched = torch.empty(Q1, dtype=torch.uint8, device=dev) if index else None
-    relconf = bits = scope = rel = conf = t_us = present = None
+    lb, matched, relconf, bits, scope = _entry_outputs(Q, dev, index, table=md != N.PAIR_RAW)
+    rel = conf = t_us = present = None
     if md == N.PAIR_RAW:
-        rel = torch.empty(Q1, dtype=torch.float64, device=dev)
-        conf = torch.empty(Q1, dtype=torch.float64, device=dev)
-        t_us = torch.empty(Q1, dtype=torch.int64, device=dev)
-        present = torch.empty(Q1, dtype=torch.uint8, device=dev)
-    else:
-        relconf = torch.empty((Q1, 2), dtype=torch.float64, device=dev)
-        bits = torch.zeros(max((Q + 31) // 32, 1), dtype=torch.int32, device=dev)
-        scope = torch.empty(Q1, dtype=torch.uint8, device=dev)
-    dense, keep = [], []
-    for x in (domain, global_scope):
-        if x is None:
-            dense += [None] * 4
-        else:
-            assert x.rel.numel() == S and x.conf.numel() == S and x.has.numel() == S and x.t_us.numel() == S, \
-                "a dense scope must have n_sources rows"
-            arrs = (x.rel.to(torch.float64).contiguous(), x.conf.to(torch.float64).contiguous(),
-                    x.t_us.to(torch.int64).contiguous(), x.has.to(torch.uint8).contiguous())
-            keep.append(arrs)  # alive until the launch is enqueued
-            dense += [N.ptr(a) for a in arrs]
-    P = pairs.n_rows
-    tab = [N.ptr(t if P else None) for t in (pairs.psid, pairs.rel, pairs.conf, pairs.t_us, pairs.has)]
+        rel, conf, t_us, present = (torch.empty(max(Q, 1), dtype=dt, device=dev)
+                                    for dt in (torch.float64, torch.float64, torch.int64, torch.uint8))
+    dom, dptr = _dense_scope(domain, S, "a dense scope must have n_sources rows")  # alive until enqueued
+    glob, gptr = _dense_scope(global_scope, S, "a dense scope must have n_sources rows")
     N.check(L.bce_pair_resolve(md, N.ptr(qoffsets), M, N.ptr(qsid if Q else None), N.ptr(emarket if Q else None), Q,
-                               N.ptr(pairs.poffsets), *tab, P, S, *dense, int(bool(apply_decay)), int(now_us),
-                               float(half_life_days), float(min_rel), DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE,
-                               int(bool(mark_cold)), N.ptr(lb), N.ptr(matched), N.ptr(relconf), N.ptr(bits),
-                               N.ptr(scope), N.ptr(rel), N.ptr(conf), N.ptr(t_us), N.ptr(present), N.stream(dev)),
-            "bce_pair_resolve")
-    cut = lambda t: None if t is None else t[:Q]  # noqa: E731
+                               N.ptr(pairs.poffsets), *_pair_pointers(pairs), pairs.n_rows, S, *dptr, *gptr,
+                               int(bool(apply_decay)), int(now_us), float(half_life_days), float(min_rel),
+                               DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE, int(bool(mark_cold)), N.ptr(lb),
+                               N.ptr(matched), N.ptr(relconf), N.ptr(bits), N.ptr(scope), N.ptr(rel), N.ptr(conf),
+                               N.ptr(t_us), N.ptr(present), N.stream(dev)), "bce_pair_resolve")
     table = SourceTable(relconf, bits, range(Q)) if relconf is not None else None  # "names": the entry indices
-    return PairResolveResult(cut(lb), cut(matched), table, cut(scope), cut(rel), cut(conf), cut(t_us), cut(present))
+    lb, matched, scope, rel, conf, t_us, present = _cut(Q, lb, matched, scope, rel, conf, t_us, present)
+    return PairResolveResult(lb, matched, table, scope, rel, conf, t_us, present)
 
 
 @dataclass
@@ -1244,8 +1278,7 @@ def consensus_pairs(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor
         plan = PairPlan.build(offsets, sid, prob, pairs.n_sources)
     if plan.n_markets != pairs.n_markets or plan.n_sources != pairs.n_sources:
         raise ValueError("the plan and the pair table describe different batches")
-    if "bins" in consensus_kwargs:
-        consensus_kwargs["plan"] = consensus_kwargs.pop("bins")
+    _bins_as_plan(consensus_kwargs)
     if per_market:
         lb, matched, dlb, dmatched, table, scope = scope_resolve(
             plan.uoffsets, plan.usid, pairs, domains, market_domain, now_us, emarket=plan.emarket,
@@ -1516,9 +1549,7 @@ def walk_forward(plan: WalkPlan, table: "ReliabilityTable", market_time_us: torc
         raise ValueError("offsets / prob are not the batch the plan was built from")
     wtable, exists = walk_trace(plan, table, market_time_us, all_present=all_present, long_min=long_min,
                                 chunk_bits=chunk_bits)
-    if "bins" in consensus_kwargs:
-        consensus_kwargs["plan"] = consensus_kwargs.pop("bins")
-    res = consensus(offsets, pp.esid, prob.to(torch.float64), wtable, mode=mode, **consensus_kwargs)
+    res = consensus(offsets, pp.esid, prob.to(torch.float64), wtable, mode=mode, **_bins_as_plan(consensus_kwargs))
     if commit and sp.n_touched:
         kw = {}
         if long_min is not None:
@@ -1555,50 +1586,26 @@ def scope_resolve(qoffsets: torch.Tensor, qsid: torch.Tensor, pairs: Optional[Pa
     skips the four index outputs.  A ``market_domain`` outside ``[-1, D)`` or offsets that are
     no segments raise the device fault word (``_native.check_faults``)."""
     L = N.require_gpu()
-    M, Q, S, D = market_domain.numel(), qsid.numel(), domains.n_sources, domains.n_markets
-    if qoffsets.numel() != M + 1:
-        raise ValueError(f"qoffsets must have n_markets + 1 = {M + 1} entries")
+    M, S, D = market_domain.numel(), domains.n_sources, domains.n_markets
     if pairs is not None and (pairs.n_markets != M or pairs.n_sources != S):
         raise ValueError("the pair table, the domain table and market_domain describe different batches")
-    if emarket is not None and emarket.numel() != Q:
-        raise ValueError("emarket and qsid differ in length")
+    Q = _check_queries(qoffsets, qsid, emarket, M)
     dev = qoffsets.device
-    assert qoffsets.dtype == torch.int64 and qsid.dtype == torch.int32, "qoffsets int64, qsid int32"
-    assert emarket is None or emarket.dtype == torch.int32, "emarket must be int32"
     assert market_domain.dtype == torch.int32, "market_domain must be int32"
-    Q1 = max(Q, 1)
-    lb = matched = dlb = dmatched = None
-    if index:
-        lb = torch.empty(Q1, dtype=torch.int64, device=dev)
-        matched = torch.empty(Q1, dtype=torch.uint8, device=dev)
-        dlb = torch.empty(Q1, dtype=torch.int64, device=dev)
-        dmatched = torch.empty(Q1, dtype=torch.uint8, device=dev)
-    relconf = torch.empty((Q1, 2), dtype=torch.float64, device=dev)
-    bits = torch.zeros(max((Q + 31) // 32, 1), dtype=torch.int32, device=dev)
-    scope = torch.empty(Q1, dtype=torch.uint8, device=dev)
-    glob = [None] * 4
-    if global_scope is not None:
-        x = global_scope
-        assert x.rel.numel() == S and x.conf.numel() == S and x.has.numel() == S and x.t_us.numel() == S, \
-            "the global scope must have n_sources rows"
-        glob = (x.rel.to(torch.float64).contiguous(), x.conf.to(torch.float64).contiguous(),
-                x.t_us.to(torch.int64).contiguous(), x.has.to(torch.uint8).contiguous())  # alive until enqueued
-    P = pairs.n_rows if pairs is not None else 0
-    R = domains.n_rows
-    ptab = [N.ptr(t if P else None) for t in ((pairs.psid, pairs.rel, pairs.conf, pairs.t_us, pairs.has)
-                                              if pairs is not None else [None] * 5)]
-    dtab = [N.ptr(t if R else None) for t in (domains.psid, domains.rel, domains.conf, domains.t_us, domains.has)]
+    lb, matched, relconf, bits, scope = _entry_outputs(Q, dev, index)
+    dlb, dmatched = _entry_outputs(Q, dev, index, table=False)[:2]
+    glob, gptr = _dense_scope(global_scope, S, "the global scope must have n_sources rows")  # alive until enqueued
     mdom = market_domain.contiguous()
     N.check(L.bce_scope_resolve(N.ptr(qoffsets), M, N.ptr(qsid if Q else None), N.ptr(emarket if Q else None), Q,
-                                N.ptr(pairs.poffsets if pairs is not None else None), *ptab, P,
-                                N.ptr(mdom if M else None), N.ptr(domains.poffsets), D, *dtab, R, S,
-                                *[N.ptr(g) for g in glob], int(bool(apply_decay)), int(now_us),
-                                float(half_life_days), float(min_rel), DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE,
-                                int(bool(mark_cold)), N.ptr(lb), N.ptr(matched), N.ptr(dlb), N.ptr(dmatched),
-                                N.ptr(relconf), N.ptr(bits), N.ptr(scope), N.stream(dev)), "bce_scope_resolve")
-    cut = lambda t: None if t is None else t[:Q]  # noqa: E731
+                                N.ptr(pairs.poffsets if pairs is not None else None), *_pair_pointers(pairs),
+                                pairs.n_rows if pairs is not None else 0, N.ptr(mdom if M else None),
+                                N.ptr(domains.poffsets), D, *_pair_pointers(domains), domains.n_rows, S, *gptr,
+                                int(bool(apply_decay)), int(now_us), float(half_life_days), float(min_rel),
+                                DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE, int(bool(mark_cold)), N.ptr(lb),
+                                N.ptr(matched), N.ptr(dlb), N.ptr(dmatched), N.ptr(relconf), N.ptr(bits),
+                                N.ptr(scope), N.stream(dev)), "bce_scope_resolve")
     table = SourceTable(relconf, bits, range(Q))  # "names": the entry indices
-    return cut(lb), cut(matched), cut(dlb), cut(dmatched), table, cut(scope)
+    return (*_cut(Q, lb, matched, dlb, dmatched), table, *_cut(Q, scope))
 
 
 @dataclass

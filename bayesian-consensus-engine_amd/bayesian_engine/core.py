@@ -113,6 +113,54 @@ def _no_signals() -> dict[str, Any]:
     }
 
 
+def signals_csr(signal_lists, rank, settlement: bool = False):
+    """The signal dicts of M markets as the CSR arrays ``(offsets int64[M+1], sid int32[N], prob
+    fp64[N])`` of :mod:`bayesian_engine.batch`.  ``rank`` maps a sourceId to its rank: one mapping
+    for the batch, or a callable ``(market position, signals) -> mapping`` for ranks of the
+    market's own, called when the market is reached.  The probability is read by the consensus
+    rule -- ``s["probability"]``, a non-number raising builtin sum()'s TypeError (core.py:116) --
+    or, ``settlement=True``, by the settlement rule: ``s.get("probability", 0.5)``, a non-number
+    raising the TypeError of ``prob >= 0.5`` (market.py:299).  Signals are visited in order, the
+    sourceId before the probability, so the first bad signal is the one that raises."""
+    offsets, sid, prob = [0], [], []
+    for mpos, signals in enumerate(signal_lists):
+        ranks = rank(mpos, signals) if callable(rank) else rank
+        for s in signals:
+            sid.append(ranks[s["sourceId"]])
+            if settlement:
+                p = s.get("probability", 0.5)
+                if not isinstance(p, (int, float)):
+                    p >= 0.5  # noqa: B015
+            else:
+                p = s["probability"]
+                if not isinstance(p, (int, float)):
+                    0 + p  # noqa: B018
+            prob.append(float(p))
+        offsets.append(len(sid))
+    return np.array(offsets, np.int64), np.array(sid, np.int32), np.array(prob, np.float64)
+
+
+def consensus_dict(ids, weight, nweight, consensus, confidence, total_weight, n_signals: int, cold,
+                   market_id: str | None = None) -> dict[str, Any]:
+    """One market of a batched result as compute_consensus's dict (core.py:145-179): ``ids`` its
+    sources in sorted() order, ``weight`` / ``nweight`` their slices, ``cold`` the cold-start
+    list; ``market_id`` adds the "marketId" key MarketStore's results carry."""
+    u = len(ids)
+    null = total_weight == 0  # core.py:131
+    out = {
+        "schemaVersion": SCHEMA_VERSION,
+        "consensus": None if null else float(consensus),
+        "confidence": 0.0 if null else float(confidence),
+        "sourceWeights": [{"sourceId": ids[j], "weight": float(weight[j]), "normalizedWeight": float(nweight[j])}
+                          for j in range(u)],
+        "normalization": {"totalWeight": float(total_weight), "sourceCount": u},
+        "diagnostics": {"status": "computed", "sources": n_signals, "uniqueSources": u, "coldStartSources": cold},
+    }
+    if market_id is not None:
+        out["marketId"] = market_id
+    return out
+
+
 def _check_number(x, other) -> None:
     """Raise the reference's TypeError for a non-numeric operand (core.py:116/120/142)."""
     if not isinstance(x, (int, float)):

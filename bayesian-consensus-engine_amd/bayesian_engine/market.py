@@ -33,8 +33,8 @@ import torch
 
 from . import _native as N
 from . import batch
-from .config import DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY, SCHEMA_VERSION
-from .core import compute_consensus
+from .config import DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY
+from .core import compute_consensus, consensus_dict, signals_csr
 from .reliability import SQLiteReliabilityStore
 from .reliability_abstraction import NamespacedReliabilityStore
 from . import decay as _decay
@@ -230,85 +230,64 @@ def _domain_fn(domain_of):
     return domain_of
 
 
+class _FirstSeen(dict):
+    """sourceId -> rank in first-seen order: looking up a new id ranks it."""
+
+    def __missing__(self, key):
+        self[key] = rank = len(self)
+        return rank
+
+
 def _batched_consensus(markets: List[Market], store: Optional[SQLiteReliabilityStore]) -> Dict[str, Dict[str, Any]]:
     """CSR over the markets, ranks over (market position, sorted sourceId)."""
-    per_market_ids = []
+    per_market_ids: List[List[str]] = []
     key_names: List[str] = []
-    offsets = [0]
-    sid_list: List[int] = []
-    prob_list: List[float] = []
-    base = 0
-    for mpos, market in enumerate(markets):
-        ids = sorted({s["sourceId"] for s in market.signals})
-        rank = {sid: base + i for i, sid in enumerate(ids)}
-        per_market_ids.append((base, ids))
+
+    def rank_market(mpos, signals):
+        ids = sorted({s["sourceId"] for s in signals})
+        base = len(key_names)
+        per_market_ids.append(ids)
         key_names.extend(ids)
-        for s in market.signals:
-            sid_list.append(rank[s["sourceId"]])
-            p = s["probability"]
-            if not isinstance(p, (int, float)):
-                0 + p  # noqa: B018  -- builtin sum()'s TypeError (core.py:116)
-            prob_list.append(float(p))
-        offsets.append(len(sid_list))
-        base += len(ids)
-    S = base
+        return {sid: base + i for i, sid in enumerate(ids)}
+
+    off, sid, prob = signals_csr([m.signals for m in markets], rank_market)
+    S = len(key_names)
     dev = N.device()
     N.require_gpu()
+    T = batch.to_device(dev)
     rel = np.full(max(S, 2), DEFAULT_RELIABILITY)
     conf = np.full(max(S, 2), DEFAULT_CONFIDENCE)
     present = np.zeros(max(S, 2), np.uint8)
     if store is not None:
         # every sourceId gets a dict entry (market.py:209-219): none is cold-start
         present[:S] = 1
-        pairs = [(sid, str(m.id)) for m, (_, ids) in zip(markets, per_market_ids) for sid in ids]
+        pairs = [(sid, str(m.id)) for m, ids in zip(markets, per_market_ids) for sid in ids]
         rows = store.fetch_pairs(pairs)
         t_us = np.full(max(S, 2), NO_TIMESTAMP, np.int64)
-        k = 0
-        for m, (_, ids) in zip(markets, per_market_ids):
-            for sid in ids:
-                row = rows.get((sid, str(m.id)))
-                if row is not None:
-                    rel[k], conf[k], t_us[k] = row[0], row[1], iso_to_us(row[2])
-                k += 1
-        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        for k, pair in enumerate(pairs):
+            row = rows.get(pair)
+            if row is not None:
+                rel[k], conf[k], t_us[k] = row[0], row[1], iso_to_us(row[2])
         rt = batch.ReliabilityTable(T(rel[:S]), T(conf[:S]), T(t_us[:S]), T(present[:S]), key_names)
         # get_reliability(apply_decay=True) for every pair, "now" read like decay.py:136-137
         table = rt.consensus_table(dt_to_us(_decay.datetime.now(timezone.utc)))
     else:
-        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
         table = batch.SourceTable.from_arrays(T(rel[:S]), T(conf[:S]), T(present[:S]), key_names)
-    off = np.array(offsets, np.int64)
-    T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
-    res = batch.consensus(T(off), T(np.array(sid_list, np.int32)), T(np.array(prob_list, np.float64)), table,
-                          validate=False, check=True)
-    cons = res.consensus.cpu().numpy()
-    confd = res.confidence.cpu().numpy()
-    tot = res.total_weight.cpu().numpy()
-    usid = res.usid.cpu().numpy()
-    weight = res.weight.cpu().numpy()
-    nweight = res.nweight.cpu().numpy()
+    res = batch.consensus(T(off), T(sid), T(prob), table, validate=False, check=True)
+    return _render_markets(markets, per_market_ids, off, res)
+
+
+def _render_markets(markets: List[Market], per_market_ids, offsets, res) -> Dict[str, Dict[str, Any]]:
+    """The dicts of a batch: market i's sorted sourceIds are ``per_market_ids[i]`` and its unique
+    slots start at ``offsets[i]``; a set sign bit of ``usid`` marks a cold-start source."""
+    cons, confd, tot, usid, weight, nweight = (x.cpu().numpy() for x in (
+        res.consensus, res.confidence, res.total_weight, res.usid, res.weight, res.nweight))
     out = {}
-    for mpos, market in enumerate(markets):
-        b, ids = per_market_ids[mpos]
-        a = offsets[mpos]
-        u = len(ids)
-        null = tot[mpos] == 0
-        sw = [{"sourceId": ids[j], "weight": float(weight[a + j]), "normalizedWeight": float(nweight[a + j])}
-              for j in range(u)]
-        out[str(market.id)] = {
-            "schemaVersion": SCHEMA_VERSION,
-            "consensus": None if null else float(cons[mpos]),
-            "confidence": 0.0 if null else float(confd[mpos]),
-            "sourceWeights": sw,
-            "normalization": {"totalWeight": float(tot[mpos]), "sourceCount": u},
-            "diagnostics": {
-                "status": "computed",
-                "sources": len(market.signals),
-                "uniqueSources": u,
-                "coldStartSources": [ids[j] for j in range(u) if usid[a + j] < 0],
-            },
-            "marketId": str(market.id),
-        }
+    for mpos, (market, ids) in enumerate(zip(markets, per_market_ids)):
+        a, b = offsets[mpos], offsets[mpos] + len(ids)
+        out[str(market.id)] = consensus_dict(ids, weight[a:b], nweight[a:b], cons[mpos], confd[mpos], tot[mpos],
+                                             len(market.signals), [s for s, r in zip(ids, usid[a:b]) if r < 0],
+                                             str(market.id))
     return out
 
 
@@ -323,20 +302,10 @@ def _batched_consensus_pairs(markets: List[Market], store, domain_of=None) -> Di
     market carries its domain (``batch.consensus_pairs(domains=, market_domain=)``)."""
     rank = batch.intern(s["sourceId"] for m in markets for s in m.signals)
     names = list(rank)
-    offsets = [0]
-    sid_list: List[int] = []
-    prob_list: List[float] = []
-    for market in markets:
-        for s in market.signals:
-            sid_list.append(rank[s["sourceId"]])
-            p = s["probability"]
-            if not isinstance(p, (int, float)):
-                0 + p  # noqa: B018  -- builtin sum()'s TypeError (core.py:116)
-            prob_list.append(float(p))
-        offsets.append(len(sid_list))
+    off, sid, prob = signals_csr([m.signals for m in markets], rank)
     N.require_gpu()
     dev = N.device()
-    T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+    T = batch.to_device(dev)
     namespaced = {}
     if domain_of is not None:
         doms = [domain_of(m) for m in markets]
@@ -350,41 +319,12 @@ def _batched_consensus_pairs(markets: List[Market], store, domain_of=None) -> Di
     pairs = store.load_pair_table([str(m.id) for m in markets], names, device=dev)
     # get_reliability(apply_decay=True) for every pair, "now" read like decay.py:136-137
     now_us = dt_to_us(_decay.datetime.now(timezone.utc))
-    pc = batch.consensus_pairs(T(np.array(offsets, np.int64)), T(np.array(sid_list, np.int32)),
-                               T(np.array(prob_list, np.float64)), pairs, now_us, validate=False, check=True,
-                               **namespaced)
-    res = pc.result
-    cons = res.consensus.cpu().numpy()
-    confd = res.confidence.cpu().numpy()
-    tot = res.total_weight.cpu().numpy()
-    usid = res.usid.cpu().numpy()
-    weight = res.weight.cpu().numpy()
-    nweight = res.nweight.cpu().numpy()
+    pc = batch.consensus_pairs(T(off), T(sid), T(prob), pairs, now_us, validate=False, check=True, **namespaced)
     uoff = pc.plan.uoffsets.cpu().numpy()
     esrc = pc.plan.usid.cpu().numpy()
-    out = {}
-    for mpos, market in enumerate(markets):
-        ids = [names[s] for s in esrc[uoff[mpos]:uoff[mpos + 1]]]  # sorted(): entries ascend with the rank
-        a = offsets[mpos]
-        u = len(ids)
-        null = tot[mpos] == 0
-        sw = [{"sourceId": ids[j], "weight": float(weight[a + j]), "normalizedWeight": float(nweight[a + j])}
-              for j in range(u)]
-        out[str(market.id)] = {
-            "schemaVersion": SCHEMA_VERSION,
-            "consensus": None if null else float(cons[mpos]),
-            "confidence": 0.0 if null else float(confd[mpos]),
-            "sourceWeights": sw,
-            "normalization": {"totalWeight": float(tot[mpos]), "sourceCount": u},
-            "diagnostics": {
-                "status": "computed",
-                "sources": len(market.signals),
-                "uniqueSources": u,
-                "coldStartSources": [ids[j] for j in range(u) if usid[a + j] < 0],
-            },
-            "marketId": str(market.id),
-        }
-    return out
+    # sorted(): entries ascend with the rank
+    ids = [[names[s] for s in esrc[uoff[mpos]:uoff[mpos + 1]]] for mpos in range(len(markets))]
+    return _render_markets(markets, ids, off, pc.result)
 
 
 @dataclass
@@ -443,37 +383,20 @@ class CrossMarketAggregator:
                           device_match: Optional[bool] = None) -> Dict[str, SourcePerformance]:
         markets = self._select(MarketStatus.RESOLVED, patterns, device_match)
         markets = [m for m in markets if m.outcome is not None]
-        order: Dict[str, int] = {}
-        names: List[str] = []
-        market_lists: List[List[str]] = []
-        offsets = [0]
-        sid_list: List[int] = []
-        prob_list: List[float] = []
-        outcome: List[int] = []
-        for market in markets:
-            for signal in market.signals:
-                sid = signal["sourceId"]
-                if sid not in order:
-                    order[sid] = len(names)
-                    names.append(sid)
-                    market_lists.append([])
-                market_lists[order[sid]].append(str(market.id))
-                prob = signal.get("probability", 0.5)
-                if not isinstance(prob, (int, float)):
-                    prob >= 0.5  # noqa: B015  -- the reference's TypeError (market.py:299)
-                sid_list.append(order[sid])
-                prob_list.append(float(prob))
-            offsets.append(len(sid_list))
-            outcome.append(1 if market.outcome else 0)
+        order = _FirstSeen()  # a sourceId is ranked when its signal is reached, as the reference's dict fills
+        off, sid, prob = signals_csr([m.signals for m in markets], order, settlement=True)
+        names = list(order)
+        market_lists: List[List[str]] = [[] for _ in names]
+        for market, a, b in zip(markets, off[:-1], off[1:]):
+            for s in sid[a:b]:
+                market_lists[s].append(str(market.id))
+        outcome = [1 if market.outcome else 0 for market in markets]
         results: Dict[str, SourcePerformance] = {}
         if not names:
             return results
         N.require_gpu()
-        dev = N.device()
-        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
-        correct, total = batch.agreement_stats(T(np.array(offsets, np.int64)), T(np.array(sid_list, np.int32)),
-                                               T(np.array(prob_list, np.float64)), T(np.array(outcome, np.int8)),
-                                               len(names))
+        T = batch.to_device(N.device())
+        correct, total = batch.agreement_stats(T(off), T(sid), T(prob), T(np.array(outcome, np.int8)), len(names))
         correct = correct.cpu().numpy()
         total = total.cpu().numpy()
         for i, sid in enumerate(names):
@@ -498,25 +421,14 @@ class CrossMarketAggregator:
         if not markets:
             return results
         rank = batch.intern(signal["sourceId"] for m in markets for signal in m.signals)
-        offsets = [0]
-        sid_list: List[int] = []
-        prob_list: List[float] = []
+        off, sid, prob = signals_csr([m.signals for m in markets], rank, settlement=True)
         known: List[int] = []
         for market in markets:
-            for signal in market.signals:
-                prob = signal.get("probability", 0.5)
-                if not isinstance(prob, (int, float)):
-                    prob >= 0.5  # noqa: B015  -- the reference's TypeError (market.py:299)
-                sid_list.append(rank[signal["sourceId"]])
-                prob_list.append(float(prob))
-            offsets.append(len(sid_list))
             resolved = market.status == MarketStatus.RESOLVED and market.outcome is not None
             known.append((1 if market.outcome else 0) if resolved else -1)
         N.require_gpu()
-        dev = N.device()
-        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
-        plan = batch.ReestimateCsrPlan.build(T(np.array(offsets, np.int64)), T(np.array(sid_list, np.int32)),
-                                             T(np.array(prob_list, np.float64)), len(rank))
+        T = batch.to_device(N.device())
+        plan = batch.ReestimateCsrPlan.build(T(off), T(sid), T(prob), len(rank))
         r = batch.reestimate_csr(plan, iters, w0=prior, known=T(np.array(known, np.int8)))
         w = r.w.cpu().numpy()
         correct = r.correct.cpu().numpy()
@@ -644,7 +556,7 @@ class CrossMarketAggregator:
                     raise ValueError(f"Unknown aggregation method: {method}")
         N.require_gpu()
         dev = N.device()
-        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        T = batch.to_device(dev)
         goff = np.zeros(len(groups) + 1, np.int64)
         goff[1:] = np.cumsum([len(g) for g in groups])
         flat = np.array([m for g in groups for m in g], np.int64)
@@ -714,7 +626,7 @@ class CrossMarketAggregator:
             return [dict(empty, marketsIncluded=int(n)) for n in sizes]
         if method not in ("weighted_average", "median", "majority"):
             raise ValueError(f"Unknown aggregation method: {method}")  # some group has a consensus
-        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        T = batch.to_device(dev)
         r = batch.aggregate(goff, members, T(cons), T(conf), T(has), median=method == "median")
         pick = {"weighted_average": r.wavg, "median": r.median, "majority": r.majority}[method].cpu().numpy()
         mconf = r.mean_conf.cpu().numpy()

@@ -87,6 +87,16 @@ class ReliabilityRecord:
     updated_at: str
 
 
+def _as_tensor(a, dev, dtype) -> torch.Tensor:
+    """An array or a tensor as a tensor of ``dtype`` on ``dev``."""
+    return torch.as_tensor(np.asarray(a) if not isinstance(a, torch.Tensor) else a).to(dev, dtype)
+
+
+def _csr_tensors(dev, offsets, sid, prob, outcome):
+    return (_as_tensor(offsets, dev, torch.int64), _as_tensor(sid, dev, torch.int32),
+            _as_tensor(prob, dev, torch.float64), _as_tensor(outcome, dev, torch.int8))
+
+
 def _update_one_gpu(r: float, c: float, correct: bool) -> tuple:
     """reliability.py:163-173 for one row, through the batched update kernel."""
     N.require_gpu()
@@ -172,6 +182,12 @@ class SQLiteReliabilityStore:
     def _ensure_schema(self) -> None:
         self._conn.executescript(_CREATE_TABLE_SQL)
 
+    def _upsert(self, rows) -> None:
+        """Rows ``(source_id, market_id, reliability, confidence, updated_at)`` in one transaction."""
+        with self._conn:
+            self._conn.execute("BEGIN")
+            self._conn.executemany(_UPSERT_SQL, rows)
+
     # ------------------------------------------------------------------ bulk paths (f1)
     def load_table(self, market_id: str, names: Optional[Sequence[str]] = None,
                    device=None) -> batch.ReliabilityTable:
@@ -198,7 +214,7 @@ class SQLiteReliabilityStore:
             t_us[p] = iso_to_us_many(cols[3])[keep]
             present[p] = 1
         dev = device or N.device()
-        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        T = batch.to_device(dev)
         return batch.ReliabilityTable(T(rel), T(conf), T(t_us), T(present), list(names))
 
     def decayed_view(self, table: batch.ReliabilityTable, now: Optional[datetime] = None) -> torch.Tensor:
@@ -222,10 +238,7 @@ class SQLiteReliabilityStore:
         stamp = us_to_iso(now_us)
         out = {n: ReliabilityRecord(n, market_id, float(rel[i]), float(conf[i]), stamp) for i, n in enumerate(names)}
         if not dry_run and S:
-            with self._conn:  # one transaction
-                self._conn.execute("BEGIN")
-                self._conn.executemany(_UPSERT_SQL, [(n, market_id, float(rel[i]), float(conf[i]), stamp)
-                                                     for i, n in enumerate(names)])
+            self._upsert((n, market_id, float(rel[i]), float(conf[i]), stamp) for i, n in enumerate(names))
         return out
 
     def settle(self, market_id: str, names: Sequence[str], plan: "batch.SettlePlan", dry_run: bool = False,
@@ -251,10 +264,7 @@ class SQLiteReliabilityStore:
         out = {names[i]: ReliabilityRecord(names[i], market_id, float(rel[i]), float(conf[i]), stamp)
                for i in sorted(int(x) for x in touched)}
         if not dry_run and out:
-            with self._conn:  # one transaction
-                self._conn.execute("BEGIN")
-                self._conn.executemany(_UPSERT_SQL, [(r.source_id, market_id, r.reliability, r.confidence, stamp)
-                                                     for r in out.values()])
+            self._upsert((r.source_id, market_id, r.reliability, r.confidence, stamp) for r in out.values())
         return out
 
     _IN_CHUNK = 900  # host parameters per statement (SQLite's default limit is 999)
@@ -288,7 +298,7 @@ class SQLiteReliabilityStore:
                 conf.append(c)
                 stamps.append(ts)
         dev = device if device is not None else N.device()
-        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        T = batch.to_device(dev)
         has = np.fromiter((1 if ts else 0 for ts in stamps), np.uint8, len(stamps))
         return batch.PairTable.from_rows(T(np.asarray(mk, np.int64)), T(np.asarray(sd, np.int32)),
                                          T(np.asarray(rel, np.float64)), T(np.asarray(conf, np.float64)),
@@ -305,35 +315,13 @@ class SQLiteReliabilityStore:
         N.require_gpu()
         dev = N.device()
         market_ids = [str(m) for m in market_ids]
-        names = list(names)
-        T = lambda a, dt: torch.as_tensor(np.asarray(a) if not isinstance(a, torch.Tensor) else a).to(dev, dt)  # noqa: E731
-        offsets, sid = T(offsets, torch.int64), T(sid, torch.int32)
-        prob, outcome = T(prob, torch.float64), T(outcome, torch.int8)
+        offsets, sid, prob, outcome = _csr_tensors(dev, offsets, sid, prob, outcome)
         if offsets.numel() != len(market_ids) + 1:
             raise ValueError("offsets must have len(market_ids) + 1 entries")
         pairs = self.load_pair_table(market_ids, names, device=dev)
         plan = batch.PairPlan.build(offsets, sid, prob, pairs.n_sources)
-        now_us = dt_to_us(now or datetime.now(timezone.utc))
-        settled, splan = batch.settle_pairs(plan, pairs, offsets, prob, outcome, now_us)
-        E = plan.n_entries
-        # every touched pair now has a row: read them back per entry
-        r = batch.pair_resolve(plan.uoffsets, plan.usid, settled, now_us, mode="raw", emarket=plan.emarket)
-        touched = torch.nonzero(splan.total[:E] > 0).flatten()
-        em = plan.emarket[touched].cpu().numpy()
-        us = plan.usid[touched].cpu().numpy()
-        rel = r.rel[touched].cpu().numpy()
-        conf = r.conf[touched].cpu().numpy()
-        N.check_faults(dev, "settle_pairs")
-        stamp = us_to_iso(now_us)
-        out = {(names[int(s)], market_ids[int(m)]): ReliabilityRecord(names[int(s)], market_ids[int(m)], float(x),
-                                                                      float(c), stamp)
-               for m, s, x, c in zip(em, us, rel, conf)}
-        if not dry_run and out:
-            with self._conn:  # one transaction
-                self._conn.execute("BEGIN")
-                self._conn.executemany(_UPSERT_SQL, [(r_.source_id, r_.market_id, r_.reliability, r_.confidence,
-                                                      stamp) for r_ in out.values()])
-        return out
+        return self._settle_keyed(market_ids, names, plan, pairs, batch.settle_pairs, offsets, prob, outcome,
+                                  "settle_pairs", dry_run, now)
 
     def settle_domains(self, domain_keys: Sequence[str], names: Sequence[str], offsets, sid, prob, outcome,
                        market_domain, dry_run: bool = False,
@@ -349,35 +337,38 @@ class SQLiteReliabilityStore:
         N.require_gpu()
         dev = N.device()
         domain_keys = [str(k) for k in domain_keys]
-        names = list(names)
-        T = lambda a, dt: torch.as_tensor(np.asarray(a) if not isinstance(a, torch.Tensor) else a).to(dev, dt)  # noqa: E731
-        offsets, sid = T(offsets, torch.int64), T(sid, torch.int32)
-        prob, outcome = T(prob, torch.float64), T(outcome, torch.int8)
-        market_domain = T(market_domain, torch.int32)
+        offsets, sid, prob, outcome = _csr_tensors(dev, offsets, sid, prob, outcome)
         domains = self.load_pair_table(domain_keys, names, device=dev)
-        plan = batch.DomainPlan.build(offsets, sid, market_domain, domains.n_sources, len(domain_keys))
+        plan = batch.DomainPlan.build(offsets, sid, _as_tensor(market_domain, dev, torch.int32), domains.n_sources,
+                                      len(domain_keys))
+        return self._settle_keyed(domain_keys, names, plan, domains, batch.settle_domains, offsets, prob, outcome,
+                                  "settle_domains", dry_run, now)
+
+    def _settle_keyed(self, keys: List[str], names: Sequence[str], plan: "batch.PairPlan", table: "batch.PairTable",
+                      settle, offsets, prob, outcome, what: str, dry_run: bool,
+                      now: Optional[datetime]) -> Dict[tuple, ReliabilityRecord]:
+        """The body of :meth:`settle_pairs` / :meth:`settle_domains`: ``settle`` (the function of
+        :mod:`batch` of that name) applies the chains to ``table``, whose market index ranks
+        ``keys``; the touched rows are read back per entry of ``plan`` and upserted."""
+        names = list(names)
         now_us = dt_to_us(now or datetime.now(timezone.utc))
-        settled, splan = batch.settle_domains(plan, domains, offsets, prob, outcome, now_us)
-        F = plan.n_entries
-        out: Dict[tuple, ReliabilityRecord] = {}
-        if F:
-            # every touched pair now has a row: read them back per entry
-            r = batch.pair_resolve(plan.uoffsets, plan.usid, settled, now_us, mode="raw", emarket=plan.emarket)
-            touched = torch.nonzero(splan.total[:F] > 0).flatten()
-            ed = plan.emarket[touched].cpu().numpy()
-            us = plan.usid[touched].cpu().numpy()
-            rel = r.rel[touched].cpu().numpy()
-            conf = r.conf[touched].cpu().numpy()
-            N.check_faults(dev, "settle_domains")
-            stamp = us_to_iso(now_us)
-            out = {(names[int(s)], domain_keys[int(d)]): ReliabilityRecord(names[int(s)], domain_keys[int(d)],
-                                                                           float(x), float(c), stamp)
-                   for d, s, x, c in zip(ed, us, rel, conf)}
+        settled, splan = settle(plan, table, offsets, prob, outcome, now_us)
+        E = plan.n_entries
+        if not E:  # an empty batch, or (domains) no signal in a market with a domain
+            return {}
+        # every touched pair now has a row: read them back per entry
+        r = batch.pair_resolve(plan.uoffsets, plan.usid, settled, now_us, mode="raw", emarket=plan.emarket)
+        touched = torch.nonzero(splan.total[:E] > 0).flatten()
+        ek = plan.emarket[touched].cpu().numpy()
+        us = plan.usid[touched].cpu().numpy()
+        rel = r.rel[touched].cpu().numpy()
+        conf = r.conf[touched].cpu().numpy()
+        N.check_faults(offsets.device, what)
+        stamp = us_to_iso(now_us)
+        out = {(names[int(s)], keys[int(k)]): ReliabilityRecord(names[int(s)], keys[int(k)], float(x), float(c), stamp)
+               for k, s, x, c in zip(ek, us, rel, conf)}
         if not dry_run and out:
-            with self._conn:  # one transaction
-                self._conn.execute("BEGIN")
-                self._conn.executemany(_UPSERT_SQL, [(r_.source_id, r_.market_id, r_.reliability, r_.confidence,
-                                                      r_.updated_at) for r_ in out.values()])
+            self._upsert((r_.source_id, r_.market_id, r_.reliability, r_.confidence, stamp) for r_ in out.values())
         return out
 
     def fetch_pairs(self, pairs: Sequence[tuple]) -> Dict[tuple, tuple]:

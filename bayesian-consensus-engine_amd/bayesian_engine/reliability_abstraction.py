@@ -19,12 +19,11 @@ from enum import Enum
 from typing import List, Optional, Protocol, Sequence, Tuple, runtime_checkable
 
 import numpy as np
-import torch
 
 from . import _native as N
 from . import batch
-from .config import DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY, SCHEMA_VERSION
-from .core import _no_signals as core_no_signals
+from .config import DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY
+from .core import _no_signals as core_no_signals, consensus_dict, signals_csr
 from .reliability import SQLiteReliabilityStore
 from .timeutil import NO_TIMESTAMP, dt_to_us, iso_to_us, us_to_iso
 
@@ -78,6 +77,16 @@ class ReliabilityProvider(Protocol):
         ...
 
 
+def _namespaced(r, namespace: ReliabilityNamespace, value: str) -> NamespacedReliabilityRecord:
+    """A settled :class:`ReliabilityRecord` as the record of its namespace."""
+    return NamespacedReliabilityRecord(r.source_id, namespace, value, r.reliability, r.confidence, r.updated_at, False)
+
+
+def _outcome_codes(markets) -> np.ndarray:
+    """int8 per ``(signals, outcome)``: -1 unresolved (None), else the outcome's truth."""
+    return np.array([-1 if o is None else (1 if o else 0) for _, o in markets], np.int8)
+
+
 # scope code (bce_namespace_resolve) -> (namespace, is_fallback)
 _SCOPE_NS = {batch.NS_MARKET: (ReliabilityNamespace.MARKET, False),
              batch.NS_DOMAIN: (ReliabilityNamespace.DOMAIN, True),
@@ -119,17 +128,20 @@ class NamespacedReliabilityStore:
     def update_reliability(self, source_id: str, outcome_correct: bool, market_id: Optional[str] = None,
                            domain: Optional[str] = None, update_global: bool = False) -> NamespacedReliabilityRecord:
         """reliability_abstraction.py:190-240."""
-        if market_id:
-            namespace, namespace_value, target = ReliabilityNamespace.MARKET, market_id, market_id
-        elif domain:
-            namespace, namespace_value, target = ReliabilityNamespace.DOMAIN, domain, f"__domain__:{domain}"
-        else:
-            namespace, namespace_value, target = ReliabilityNamespace.GLOBAL, "global", self.GLOBAL_MARKET_ID
+        namespace, namespace_value, target = self._update_scope(domain, market_id)
         record = self._store.update_reliability(source_id, target, outcome_correct)
         if update_global and namespace != ReliabilityNamespace.GLOBAL:
             self._store.update_reliability(source_id, self.GLOBAL_MARKET_ID, outcome_correct)
         return NamespacedReliabilityRecord(source_id, namespace, namespace_value, record.reliability,
                                            record.confidence, record.updated_at, False)
+
+    def _update_scope(self, domain: Optional[str], market_id: Optional[str] = None):
+        """``(namespace, namespace_value, scope key)`` an update goes to (reliability_abstraction.py:211-216)."""
+        if market_id:
+            return ReliabilityNamespace.MARKET, market_id, market_id
+        if domain:
+            return ReliabilityNamespace.DOMAIN, domain, f"__domain__:{domain}"
+        return ReliabilityNamespace.GLOBAL, "global", self.GLOBAL_MARKET_ID
 
     def set_global_reliability(self, source_id: str, reliability: float,
                                confidence: float) -> NamespacedReliabilityRecord:
@@ -175,7 +187,7 @@ class NamespacedReliabilityStore:
             if i is None or not ts:  # the reference only takes rows with a truthy updated_at
                 continue
             rel[i], conf[i], t_us[i], has[i], stamps[i] = r, c, iso_to_us(ts), 1, ts
-        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        T = batch.to_device(dev)
         return batch.ScopeTable(T(rel), T(conf), T(t_us), T(has)), stamps
 
     def resolve(self, names: Sequence[str], market_id: Optional[str] = None, domain: Optional[str] = None,
@@ -255,50 +267,24 @@ class NamespacedReliabilityStore:
                 raise ValueError("duplicate market id in market_ids")
         rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
         names = list(rank)
-        offsets = [0]
-        sid_list: List[int] = []
-        prob_list: List[float] = []
-        outcome_list: List[int] = []
-        for signals, outcome in markets:
-            for s in signals:
-                prob = s.get("probability", 0.5)
-                if not isinstance(prob, (int, float)):
-                    prob >= 0.5  # noqa: B015  -- the reference's TypeError (market.py:299)
-                sid_list.append(rank[s["sourceId"]])
-                prob_list.append(float(prob))
-            offsets.append(len(sid_list))
-            outcome_list.append(-1 if outcome is None else (1 if outcome else 0))
-        if domain:
-            namespace, value, target = ReliabilityNamespace.DOMAIN, domain, f"__domain__:{domain}"
-        else:
-            namespace, value, target = ReliabilityNamespace.GLOBAL, "global", self.GLOBAL_MARKET_ID
+        offsets, sid, prob = signals_csr([signals for signals, _ in markets], rank, settlement=True)
+        outcomes = _outcome_codes(markets)
+        namespace, value, target = self._update_scope(domain)
         if not names:
             return SettleSummary({}, {}, {}, {})
         N.require_gpu()
         dev = N.device()
-        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        T = batch.to_device(dev)
         if domains is not None and market_ids is None:
-            return self._settle_per_domain(markets, domains, names, np.array(offsets, np.int64),
-                                           np.array(sid_list, np.int32), np.array(prob_list, np.float64),
-                                           np.array(outcome_list, np.int8), update_global, dry_run,
-                                           now or datetime.now(timezone.utc))
-        plan = batch.SettlePlan.build(T(np.array(offsets, np.int64)), T(np.array(sid_list, np.int32)),
-                                      T(np.array(prob_list, np.float64)), T(np.array(outcome_list, np.int8)),
-                                      len(names))
+            return self._settle_per_domain(markets, domains, names, offsets, sid, prob, outcomes, update_global,
+                                           dry_run, now or datetime.now(timezone.utc))
+        plan = batch.SettlePlan.build(T(offsets), T(sid), T(prob), T(outcomes), len(names))
         now = now or datetime.now(timezone.utc)
         if market_ids is not None:
             mids = [str(m) for m in market_ids]
-            precs = self._store.settle_pairs(mids, names, np.array(offsets, np.int64), np.array(sid_list, np.int32),
-                                             np.array(prob_list, np.float64), np.array(outcome_list, np.int8),
-                                             dry_run=dry_run, now=now)
-            records = {k: NamespacedReliabilityRecord(k[0], ReliabilityNamespace.MARKET, k[1], r.reliability,
-                                                      r.confidence, r.updated_at, False) for k, r in precs.items()}
-            global_records = {}
-            if update_global:
-                grecs = self._store.settle(self.GLOBAL_MARKET_ID, names, plan, dry_run=dry_run, now=now)
-                global_records = {sid: NamespacedReliabilityRecord(sid, ReliabilityNamespace.GLOBAL, "global",
-                                                                   r.reliability, r.confidence, r.updated_at, False)
-                                  for sid, r in grecs.items()}
+            precs = self._store.settle_pairs(mids, names, offsets, sid, prob, outcomes, dry_run=dry_run, now=now)
+            records = {k: _namespaced(r, ReliabilityNamespace.MARKET, k[1]) for k, r in precs.items()}
+            global_records = self._settle_global(names, plan, dry_run, now) if update_global else {}
             ptotal = dict.fromkeys(records, 0)
             pcorrect = dict.fromkeys(records, 0)
             for mid, (signals, outcome) in zip(mids, markets):
@@ -310,18 +296,19 @@ class NamespacedReliabilityStore:
                     pcorrect[k] += int((s.get("probability", 0.5) >= 0.5) == bool(outcome))
             return SettleSummary(records, global_records, ptotal, pcorrect)
         recs = self._store.settle(target, names, plan, dry_run=dry_run, now=now)
-        records = {sid: NamespacedReliabilityRecord(sid, namespace, value, r.reliability, r.confidence,
-                                                    r.updated_at, False) for sid, r in recs.items()}
+        records = {sid: _namespaced(r, namespace, value) for sid, r in recs.items()}
         global_records = {}
         if update_global and namespace != ReliabilityNamespace.GLOBAL:
-            grecs = self._store.settle(self.GLOBAL_MARKET_ID, names, plan, dry_run=dry_run, now=now)
-            global_records = {sid: NamespacedReliabilityRecord(sid, ReliabilityNamespace.GLOBAL, "global",
-                                                               r.reliability, r.confidence, r.updated_at, False)
-                              for sid, r in grecs.items()}
+            global_records = self._settle_global(names, plan, dry_run, now)
         total = plan.total.cpu().numpy()
         correct = plan.correct.cpu().numpy()
         return SettleSummary(records, global_records, {sid: int(total[rank[sid]]) for sid in records},
                              {sid: int(correct[rank[sid]]) for sid in records})
+
+    def _settle_global(self, names, plan, dry_run, now) -> dict:
+        """``plan`` applied to ``__global__``: the records of the touched sources."""
+        grecs = self._store.settle(self.GLOBAL_MARKET_ID, names, plan, dry_run=dry_run, now=now)
+        return {sid: _namespaced(r, ReliabilityNamespace.GLOBAL, "global") for sid, r in grecs.items()}
 
     def _settle_per_domain(self, markets, domains, names, offsets, sid, prob, outcome, update_global,
                            dry_run, now) -> "SettleSummary":
@@ -333,24 +320,19 @@ class NamespacedReliabilityStore:
         drank = {d: i for i, d in enumerate(dnames)}
         market_domain = np.array([drank[d] if d else -1 for d in domains], np.int32)
         dev = N.device()
-        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        T = batch.to_device(dev)
         records = {}
         if dnames:
             of_key = {f"__domain__:{d}": d for d in dnames}
             precs = self._store.settle_domains(list(of_key), names, offsets, sid, prob, outcome, market_domain,
                                                dry_run=dry_run, now=now)
             for (s, key), r in precs.items():
-                d = of_key[key]
-                records[(s, d)] = NamespacedReliabilityRecord(s, ReliabilityNamespace.DOMAIN, d, r.reliability,
-                                                              r.confidence, r.updated_at, False)
+                records[(s, of_key[key])] = _namespaced(r, ReliabilityNamespace.DOMAIN, of_key[key])
         gout = outcome if update_global else np.where(market_domain < 0, outcome, np.int8(-1)).astype(np.int8)
         global_records = {}
         if bool((gout >= 0).any()):
             gplan = batch.SettlePlan.build(T(offsets), T(sid), T(prob), T(gout), len(names))
-            grecs = self._store.settle(self.GLOBAL_MARKET_ID, names, gplan, dry_run=dry_run, now=now)
-            global_records = {s: NamespacedReliabilityRecord(s, ReliabilityNamespace.GLOBAL, "global", r.reliability,
-                                                             r.confidence, r.updated_at, False)
-                              for s, r in grecs.items()}
+            global_records = self._settle_global(names, gplan, dry_run, now)
         total: dict = {}
         correct: dict = {}
         for d, (signals, out) in zip(domains, markets):
@@ -385,31 +367,18 @@ class NamespacedReliabilityStore:
         t_us = np.array([iso_to_us(t) if isinstance(t, str) else dt_to_us(t) for t in times], np.int64)
         if (t_us == NO_TIMESTAMP).any():
             raise ValueError("a market time is empty or unparseable")
-        if domain:
-            namespace, value, target = ReliabilityNamespace.DOMAIN, domain, f"__domain__:{domain}"
-        else:
-            namespace, value, target = ReliabilityNamespace.GLOBAL, "global", self.GLOBAL_MARKET_ID
+        namespace, value, target = self._update_scope(domain)
         rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
         names = list(rank)
-        offsets = [0]
-        sid_list: List[int] = []
-        prob_list: List[float] = []
-        for signals, _ in markets:
-            for s in signals:
-                prob = s["probability"]
-                if not isinstance(prob, (int, float)):
-                    0 + prob  # noqa: B018  -- builtin sum()'s TypeError (core.py:116)
-                sid_list.append(rank[s["sourceId"]])
-                prob_list.append(float(prob))
-            offsets.append(len(sid_list))
-        outcome = np.array([-1 if o is None else (1 if o else 0) for _, o in markets], np.int8)
+        offsets, sid, prob = signals_csr([signals for signals, _ in markets], rank)
+        outcome = _outcome_codes(markets)
         if not names:
             return [core_no_signals() for _ in markets], SettleSummary({}, {}, {}, {})
         N.require_gpu()
         dev = N.device()
-        T = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
-        off, prob = T(np.array(offsets, np.int64)), T(np.array(prob_list, np.float64))
-        plan = batch.WalkPlan.build(off, T(np.array(sid_list, np.int32)), prob, T(outcome), len(names))
+        T = batch.to_device(dev)
+        off, prob = T(offsets), T(prob)
+        plan = batch.WalkPlan.build(off, T(sid), prob, T(outcome), len(names))
         table = self._store.load_table(target, names, device=dev)
         res = table.walk_forward(plan, T(t_us), offsets=off, prob=prob, validate=False)
         N.check_faults(dev, "walk_forward")
@@ -422,33 +391,18 @@ class NamespacedReliabilityStore:
             if not signals:
                 results.append(core_no_signals())
                 continue
-            a, u = offsets[m], int(n_unique[m])
-            ids = [names[esrc[usid[a + j] & 0x7FFFFFFF]] for j in range(u)]
-            null = tot[m] == 0
-            results.append({
-                "schemaVersion": SCHEMA_VERSION,
-                "consensus": None if null else float(cons[m]),
-                "confidence": 0.0 if null else float(confd[m]),
-                "sourceWeights": [{"sourceId": ids[j], "weight": float(weight[a + j]),
-                                   "normalizedWeight": float(nweight[a + j])} for j in range(u)],
-                "normalization": {"totalWeight": float(tot[m]), "sourceCount": u},
-                "diagnostics": {"status": "computed", "sources": len(signals), "uniqueSources": u,
-                                "coldStartSources": []},  # every source was fetched: none is cold
-            })
+            a, b = offsets[m], offsets[m] + int(n_unique[m])
+            ids = [names[esrc[e & 0x7FFFFFFF]] for e in usid[a:b]]
+            results.append(consensus_dict(ids, weight[a:b], nweight[a:b], cons[m], confd[m], tot[m], len(signals),
+                                          []))  # every source was fetched: none is cold
         touched = sorted(int(x) for x in plan.settle.order.cpu().numpy())
         rel, conf, stamp_us = table.rel.cpu().numpy(), table.conf.cpu().numpy(), table.t_us.cpu().numpy()
         total, correct = plan.total.cpu().numpy(), plan.correct.cpu().numpy()
         records = {names[i]: NamespacedReliabilityRecord(names[i], namespace, value, float(rel[i]), float(conf[i]),
                                                          us_to_iso(int(stamp_us[i])), False) for i in touched}
         if not dry_run and records:
-            with self._store._conn:  # one transaction
-                self._store._conn.execute("BEGIN")
-                self._store._conn.executemany(
-                    "INSERT INTO sources (source_id, market_id, reliability, confidence, updated_at) "
-                    "VALUES (?, ?, ?, ?, ?) ON CONFLICT(source_id, market_id) "
-                    "DO UPDATE SET reliability = excluded.reliability, confidence = excluded.confidence, "
-                    "updated_at = excluded.updated_at",
-                    [(r.source_id, target, r.reliability, r.confidence, r.updated_at) for r in records.values()])
+            self._store._upsert((r.source_id, target, r.reliability, r.confidence, r.updated_at)
+                                for r in records.values())
         return results, SettleSummary(records, {}, {names[i]: int(total[i]) for i in touched},
                                       {names[i]: int(correct[i]) for i in touched})
 

@@ -29,12 +29,4 @@ __device__ __forceinline__ double decayed(double r, int64_t t_us, const DecayCon
   return py_max(k.min_rel, py_min(1.0, d));
 }
 
-// One scope table over the S ranks (bce_namespace_resolve, bce_pair_resolve).
-struct NsScope {
-  const double* rel;
-  const double* conf;
-  const int64_t* t_us;
-  const uint8_t* has;
-};
-
 }  // namespace bce

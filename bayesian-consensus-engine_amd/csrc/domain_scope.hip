@@ -13,75 +13,26 @@
 //                         a binary search in the market's row segment, a second one in the
 //                         segment of the market's domain, the first scope whose row has a truthy
 //                         updated_at, decayed by its own t_us.  Present bits from one ballot.
-#include "bce_device.hpp"
-#include "bce_internal.hpp"
-#include "consensus_common.hpp"
-#include "decay_device.hpp"
+#include "scope_lookup.hpp"
 
 #pragma clang fp contract(off)
 
 namespace bce {
 
-struct ScopeArgs {
-  const int64_t* qoffsets;  // [M + 1]
-  int64_t M;
-  const int32_t* qsid;      // [Q]
-  const int32_t* emarket;   // [Q], nullable: search qoffsets
-  int64_t Q;
-  const int64_t* poffsets;  // [M + 1], NULL: no market scope (market_id=None)
-  const int32_t* psid;      // [P]
-  NsScope row;              // [P] the market-scope rows
-  int64_t P;
+struct ScopeArgs : LookupArgs {  // poffsets == NULL: no market scope (market_id=None)
   const int32_t* mdom;      // [M] domain index of every market, -1: none
   const int64_t* doffsets;  // [D + 1]
   int64_t D;
   const int32_t* dsid;      // [R]
   NsScope drow;             // [R] the domain-scope rows
   int64_t R;
-  int32_t S;
-  NsScope glob;             // [S] dense, rel == NULL: not requested
-  int apply_decay;
-  int mark_cold;
-  DecayConst k;
-  int64_t* lb;
-  uint8_t* matched;
   int64_t* dlb;
   uint8_t* dmatched;
-  double2* relconf;
-  uint32_t* bits;
-  uint8_t* scope;
-  int* fault;
 };
 
-constexpr int kScopeGridCap = 8192;  // workgroups (32 per CU), striding like pair_resolve_kernel
-
-// Lower bound of s in ids[lo, hi) (strictly ascending); hit = ids[lower bound] == s.  The plain
-// binary search of pair_scope.hip: a domain segment is long (up to S rows), but the lanes of a
-// wave are consecutive entries of mostly one market, so their first probes are the same words.
-__device__ __forceinline__ int64_t scope_lower_bound(const int32_t* __restrict__ ids, int64_t lo, int64_t hi,
-                                                     int32_t s, bool& hit) {
-  const int64_t end = hi;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (ids[mid] < s) lo = mid + 1; else hi = mid;
-  }
-  hit = lo < end && ids[lo] == s;
-  return lo;
-}
-
-// [o0, o1) as a segment of a table of n rows; false (and an empty segment inside the table) when
-// the pair decreases or leaves [0, n].
-__device__ __forceinline__ bool scope_segment(int64_t& o0, int64_t& o1, int64_t n) {
-  if (o0 >= 0 && o1 >= o0 && o1 <= n) return true;
-  o0 = o0 < 0 ? 0 : (o0 > n ? n : o0);
-  o1 = o0;
-  return false;
-}
-
 __global__ __launch_bounds__(256) void scope_resolve_kernel(ScopeArgs a) {
-  __shared__ unsigned long long sExp[256];  // the exp table in LDS (see replay_step_kernel)
-  sExp[threadIdx.x] = kExpTab[threadIdx.x];
-  __syncthreads();
+  __shared__ unsigned long long sExp[256];
+  stage_exp_table(sExp);
   int64_t n = a.Q > a.M ? a.Q : a.M;
   n = n > a.D ? n : a.D;
   for (int64_t base = (int64_t)blockIdx.x * 256; base < n; base += (int64_t)gridDim.x * 256) {
@@ -90,50 +41,24 @@ __global__ __launch_bounds__(256) void scope_resolve_kernel(ScopeArgs a) {
     // every market's offset pairs and domain index, and every domain's offset pair, are checked
     // once, by the lane of that index
     if (e < a.M) {
-      const int64_t q0 = a.qoffsets[e], q1 = a.qoffsets[e + 1];
-      if (q0 < 0 || q1 < q0 || q1 > a.Q) code = kFaultOffsets;
-      if (a.poffsets) {
-        const int64_t p0 = a.poffsets[e], p1 = a.poffsets[e + 1];
-        if (p0 < 0 || p1 < p0 || p1 > a.P) code = kFaultOffsets;
-      }
+      if (!is_segment(a.qoffsets[e], a.qoffsets[e + 1], a.Q)) code = kFaultOffsets;
+      if (a.poffsets && !is_segment(a.poffsets[e], a.poffsets[e + 1], a.P)) code = kFaultOffsets;
       const int64_t d = a.mdom[e];
       if (d < -1 || d >= a.D) code = kFaultOffsets;
     }
-    if (e < a.D) {
-      const int64_t d0 = a.doffsets[e], d1 = a.doffsets[e + 1];
-      if (d0 < 0 || d1 < d0 || d1 > a.R) code = kFaultOffsets;
-    }
+    if (e < a.D && !is_segment(a.doffsets[e], a.doffsets[e + 1], a.R)) code = kFaultOffsets;
     const bool in = e < a.Q;
     int sc = 3;  // cold start
     if (in) {
-      int64_t m;
-      if (a.emarket) {
-        m = a.emarket[e];
-      } else {  // the last m with qoffsets[m] <= e
-        int64_t lo = 0, hi = a.M;  // qoffsets[lo] <= e is assumed for lo = 0
-        while (hi - lo > 1) {
-          const int64_t mid = (lo + hi) >> 1;
-          if (a.qoffsets[mid] <= e) lo = mid; else hi = mid;
-        }
-        m = lo;
-      }
-      if (m < 0 || m >= a.M) {
-        code = kFaultOffsets;
-        m = m < 0 ? 0 : a.M - 1;
-      }
-      if (e < a.qoffsets[m] || e >= a.qoffsets[m + 1]) code = kFaultOffsets;  // not this market's entry
-      int32_t s = a.qsid[e];
-      if (s < 0 || s >= a.S) {
-        code = code ? code : kFaultSid;
-        s = s < 0 ? 0 : a.S - 1;
-      }
+      const int64_t m = entry_market(a.emarket, a.qoffsets, a.M, e, code);
+      const int32_t s = clamp_sid(a.qsid[e], a.S, code);
       // the market's row (absent table: market_id=None)
       bool hit = false;
       int64_t lo = 0;
       if (a.poffsets) {
         int64_t p0 = a.poffsets[m], p1 = a.poffsets[m + 1];
-        if (!scope_segment(p0, p1, a.P)) code = kFaultOffsets;  // searched as empty
-        lo = scope_lower_bound(a.psid, p0, p1, s, hit);
+        if (!clamp_segment(p0, p1, a.P)) code = kFaultOffsets;  // searched as empty
+        lo = sorted_lower_bound(a.psid, p0, p1, s, hit);
       }
       if (a.lb) a.lb[e] = lo;
       if (a.matched) a.matched[e] = hit ? 1 : 0;
@@ -147,8 +72,8 @@ __global__ __launch_bounds__(256) void scope_resolve_kernel(ScopeArgs a) {
       }
       if (d >= 0) {
         int64_t d0 = a.doffsets[d], d1 = a.doffsets[d + 1];
-        if (!scope_segment(d0, d1, a.R)) code = kFaultOffsets;  // searched as empty
-        dlo = scope_lower_bound(a.dsid, d0, d1, s, dhit);
+        if (!clamp_segment(d0, d1, a.R)) code = kFaultOffsets;  // searched as empty
+        dlo = sorted_lower_bound(a.dsid, d0, d1, s, dhit);
       }
       if (a.dlb) a.dlb[e] = dlo;
       if (a.dmatched) a.dmatched[e] = dhit ? 1 : 0;
@@ -169,21 +94,11 @@ __global__ __launch_bounds__(256) void scope_resolve_kernel(ScopeArgs a) {
         sc = 2;
       }
       double r = a.k.default_rel, c = a.k.default_conf;
-      if (pick) {
-        r = pick->rel[at];
-        c = pick->conf[at];
-        if (a.apply_decay) r = decayed(r, pick->t_us[at], a.k, sExp);
-      }
+      read_scope(pick, at, a.apply_decay, a.k, sExp, r, c);
       if (a.relconf) a.relconf[e] = make_double2(r, c);
       if (a.scope) a.scope[e] = (uint8_t)sc;
     }
-    if (a.bits) {
-      const unsigned long long w = __ballot(in && (!a.mark_cold || sc != 3));
-      const int ln = (int)(threadIdx.x & 63);
-      const int64_t w0 = (base + (threadIdx.x & ~63)) >> 5;
-      const int64_t nw = (a.Q + 31) >> 5;
-      if (ln < 2 && w0 + ln < nw) a.bits[w0 + ln] = (uint32_t)(w >> (32 * ln));
-    }
+    if (a.bits) store_present_bits(a.bits, base, a.Q, in && (!a.mark_cold || sc != 3));
     if (code && a.fault) atomicCAS(a.fault, 0, code);
   }
 }
@@ -225,40 +140,22 @@ extern "C" int bce_scope_resolve(const int64_t* qoffsets, int64_t n_markets, con
   if (grel) {
     BCE_REQUIRE(gconf && ghas && (gt_us || !apply_decay), "scope_resolve: global scope: NULL array");
   }
-  BCE_REQUIRE(relconf == nullptr || (uintptr_t)relconf % 16 == 0, "scope_resolve: relconf must be 16-byte aligned");
   ScopeArgs a{};
-  a.qoffsets = qoffsets;
-  a.M = n_markets;
-  a.qsid = qsid;
-  a.emarket = emarket;
-  a.Q = n_queries;
-  a.poffsets = poffsets;
-  a.psid = psid;
-  a.row = NsScope{prel, pconf, pt_us, phas};
-  a.P = n_rows;
+  const int rc = fill_lookup_args("scope_resolve", a, qoffsets, n_markets, qsid, emarket, n_queries, poffsets, psid,
+                                  {prel, pconf, pt_us, phas}, n_rows, n_sources, {grel, gconf, gt_us, ghas},
+                                  apply_decay, mark_cold, {now_us, half_life_days, min_rel, default_rel, default_conf},
+                                  lb, matched, relconf, present_bits, scope);
+  if (rc != BCE_OK) return rc;
   a.mdom = market_domain;
   a.doffsets = doffsets;
   a.D = n_domains;
   a.dsid = dsid;
   a.drow = NsScope{drel, dconf, dt_us, dhas};
   a.R = n_drows;
-  a.S = n_sources;
-  a.glob = NsScope{grel, gconf, gt_us, ghas};
-  a.apply_decay = apply_decay;
-  a.mark_cold = mark_cold;
-  a.k = DecayConst{now_us, half_life_days, min_rel, default_rel, default_conf};
-  a.lb = lb;
-  a.matched = matched;
   a.dlb = dlb;
   a.dmatched = dmatched;
-  a.relconf = reinterpret_cast<double2*>(relconf);
-  a.bits = present_bits;
-  a.scope = scope;
-  a.fault = fault_word();
-  int64_t n = n_queries > n_markets ? n_queries : n_markets;
-  n = n > n_domains ? n : n_domains;
-  const int64_t g = (n + 255) / 256;
-  hipLaunchKernelGGL(scope_resolve_kernel, dim3((unsigned)(g < kScopeGridCap ? g : kScopeGridCap)), dim3(256), 0,
+  const int64_t n = n_queries > n_markets ? n_queries : n_markets;
+  hipLaunchKernelGGL(scope_resolve_kernel, lookup_grid(n > n_domains ? n : n_domains), dim3(256), 0,
                      as_stream(stream), a);
   return check_launch("scope_resolve_kernel");
 }

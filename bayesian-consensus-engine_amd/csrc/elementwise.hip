@@ -7,11 +7,9 @@
 //
 // HBM-bound: each thread owns two consecutive sources so every table stream is read
 // and written with 16-byte accesses.  FP contraction off (CPython rounding).
-#include "bce_device.hpp"
-#include "bce_internal.hpp"
-#include "decay_device.hpp"  // DecayConst, decayed(), NsScope
 #include "glibc_pow.hpp"
 #include "reliability_update.hpp"
+#include "scope_lookup.hpp"  // and through it decay_device.hpp: DecayConst, decayed()
 
 #pragma clang fp contract(off)
 
@@ -193,9 +191,8 @@ __device__ __forceinline__ T ns_ld(const T* p) {
 }
 
 __global__ __launch_bounds__(256) void namespace_resolve_kernel(int64_t n, NsArgs a) {
-  __shared__ unsigned long long sExp[256];  // the exp table in LDS (see replay_step_kernel)
-  sExp[threadIdx.x] = kExpTab[threadIdx.x];
-  __syncthreads();
+  __shared__ unsigned long long sExp[256];
+  stage_exp_table(sExp);
   // whole waves walk 64 consecutive sources so the present bits come from one ballot
   for (int64_t base = (int64_t)blockIdx.x * 256; base < n; base += (int64_t)gridDim.x * 256) {
     const int64_t s = base + threadIdx.x;
@@ -231,13 +228,7 @@ __global__ __launch_bounds__(256) void namespace_resolve_kernel(int64_t n, NsArg
         if (a.scope) a.scope[s] = (uint8_t)code;
       }
     }
-    if (a.bits) {
-      const unsigned long long m = __ballot(in && (!a.mark_cold || code != 3));
-      const int ln = (int)(threadIdx.x & 63);
-      const int64_t w0 = (base + (threadIdx.x & ~63)) >> 5;
-      const int64_t nw = (n + 31) >> 5;
-      if (ln < 2 && w0 + ln < nw) a.bits[w0 + ln] = (uint32_t)(m >> (32 * ln));
-    }
+    if (a.bits) store_present_bits(a.bits, base, n, in && (!a.mark_cold || code != 3));
   }
 }
 

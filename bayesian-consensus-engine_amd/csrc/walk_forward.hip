@@ -23,11 +23,8 @@
 //                       start row, or the cold defaults where none exists.  Decays to the entry's
 //                       own market time and packs the consensus table over the entry index, the
 //                       present bits from one ballot per wave as pair_resolve_kernel does.
-#include "bce_device.hpp"
-#include "bce_internal.hpp"
-#include "consensus_common.hpp"
-#include "decay_device.hpp"
 #include "reliability_update.hpp"
+#include "scope_lookup.hpp"
 #include "settle_walk.hpp"
 
 #pragma clang fp contract(off)
@@ -199,9 +196,8 @@ struct WalkReadArgs {
 constexpr int kWalkGridCap = 8192;  // workgroups, striding like pair_resolve_kernel
 
 __global__ __launch_bounds__(256) void walk_read_kernel(WalkReadArgs a) {
-  __shared__ unsigned long long sExp[256];  // the exp table in LDS (see replay_step_kernel)
-  sExp[threadIdx.x] = kExpTab[threadIdx.x];
-  __syncthreads();
+  __shared__ unsigned long long sExp[256];
+  stage_exp_table(sExp);
   if (a.clamped && a.fault && blockIdx.x == 0 && threadIdx.x == 0) atomicCAS(a.fault, 0, kFaultSid);
   for (int64_t base = (int64_t)blockIdx.x * 256; base < a.E; base += (int64_t)gridDim.x * 256) {
     const int64_t e = base + threadIdx.x;
@@ -209,16 +205,8 @@ __global__ __launch_bounds__(256) void walk_read_kernel(WalkReadArgs a) {
     int code = 0;
     bool exists = false;
     if (in) {
-      int64_t m = a.emarket[e];
-      if (m < 0 || m >= a.M) {
-        code = kFaultOffsets;
-        m = m < 0 ? 0 : a.M - 1;
-      }
-      int32_t s = a.usid[e];
-      if (s < 0 || s >= a.S) {
-        code = code ? code : kFaultSid;
-        s = s < 0 ? 0 : a.S - 1;
-      }
+      const int64_t m = clamp_market(a.emarket[e], a.M, code);
+      const int32_t s = clamp_sid(a.usid[e], a.S, code);
       int64_t ql = a.qlast[e];
       if (ql < -1 || ql >= a.M) {  // not a market: read as "no earlier bit"
         code = kFaultOffsets;
@@ -246,11 +234,7 @@ __global__ __launch_bounds__(256) void walk_read_kernel(WalkReadArgs a) {
       a.relconf[e] = make_double2(r, c);
       if (a.exists) a.exists[e] = exists ? 1 : 0;
     }
-    const unsigned long long w = __ballot(in && (!a.mark_cold || exists));
-    const int ln = (int)(threadIdx.x & 63);
-    const int64_t w0 = (base + (threadIdx.x & ~63)) >> 5;
-    const int64_t nw = (a.E + 31) >> 5;
-    if (ln < 2 && w0 + ln < nw) a.bits[w0 + ln] = (uint32_t)(w >> (32 * ln));
+    store_present_bits(a.bits, base, a.E, in && (!a.mark_cold || exists));
     if (code && a.fault) atomicCAS(a.fault, 0, code);
   }
 }
