@@ -1339,8 +1339,16 @@ def settle_pairs(plan: PairPlan, pairs: PairTable, offsets: torch.Tensor, prob: 
         return pairs, splan
     r = pair_resolve(plan.uoffsets, plan.usid, pairs, now_us, mode="raw", emarket=plan.emarket)
     settle(splan, r.rel, r.conf, r.t_us, r.present, now_us, **settle_kwargs)
-    dst_old, ins, dst_ins, upd, dst_upd, poffsets = _pair_merge_index(r.lb, r.matched, splan.total[:E] > 0,
-                                                                      plan.emarket, pairs.poffsets)
+    return _pair_merge(plan, pairs, r, splan.total[:E] > 0), splan
+
+
+def _pair_merge(plan: PairPlan, pairs: PairTable, r: PairResolveResult, touched: torch.Tensor) -> PairTable:
+    """The settled entry table ``r`` (raw mode: ``lb`` / ``matched`` and the rows' new state over
+    the entries of ``plan``) merged into a NEW :class:`PairTable`: the ``touched`` entries
+    overwrite their matched row or are inserted in sid order (``has`` from ``r.present``), every
+    other row is carried over bit for bit."""
+    dst_old, ins, dst_ins, upd, dst_upd, poffsets = _pair_merge_index(r.lb, r.matched, touched, plan.emarket,
+                                                                      pairs.poffsets)
     P2 = pairs.n_rows + ins.numel()
     new = []
     for old, ent in ((pairs.psid, plan.usid), (pairs.rel, r.rel), (pairs.conf, r.conf), (pairs.t_us, r.t_us),
@@ -1350,7 +1358,7 @@ def settle_pairs(plan: PairPlan, pairs: PairTable, offsets: torch.Tensor, prob: 
         out.index_copy_(0, dst_ins, ent[ins])
         out.index_copy_(0, dst_upd, ent[upd])
         new.append(out)
-    return PairTable(poffsets, *new, pairs.n_markets, pairs.n_sources), splan
+    return PairTable(poffsets, *new, pairs.n_markets, pairs.n_sources)
 
 
 # ---------------------------------------------------------------------------------------
@@ -1367,29 +1375,53 @@ def _walk_queries(pairs: PairPlan, offsets: torch.Tensor, outcome: torch.Tensor)
     chain bits as it has signals; the queries are the entries in (source, market) order, ``qpos``
     the bits of the source before the entry's market, ``qlast`` (by ENTRY) the market of the last
     of those bits and ``slast`` (by source) the source's last resolved market, -1 where none."""
-    E, S, M = pairs.n_entries, pairs.n_sources, pairs.n_markets
-    dev = offsets.device
-    i64 = dict(dtype=torch.int64, device=dev)
-    usid = pairs.usid[:E].to(torch.int64)
+    E = pairs.n_entries
     emarket = pairs.emarket[:E].to(torch.int64)
-    cnt = torch.bincount(pairs.esid.to(torch.int64), minlength=E)[:E] if E else torch.zeros(0, **i64)
-    cnt = cnt * (outcome[emarket] >= 0)
-    skey, qentry = torch.sort(usid, stable=True)  # entries ascend by market: (source, market) order
-    qstart = torch.zeros(S + 1, **i64)
-    qstart[1:] = torch.cumsum(torch.bincount(usid, minlength=S), 0)
+    cnt = _entry_signals(pairs) * (outcome[emarket] >= 0)
+    return _chain_queries(pairs.usid[:E].to(torch.int64), cnt, emarket, pairs.n_sources)
+
+
+def _entry_signals(pairs: PairPlan) -> torch.Tensor:
+    """int64[E]: the signals of every entry."""
+    E = pairs.n_entries
+    if not E:
+        return torch.zeros(0, dtype=torch.int64, device=pairs.esid.device)
+    return torch.bincount(pairs.esid.to(torch.int64), minlength=E)[:E]
+
+
+def _chain_queries(chain: torch.Tensor, cnt: torch.Tensor, emarket: torch.Tensor, n_chains: int,
+                   partial: bool = False):
+    """:func:`_walk_queries` for any family of chains over the entries (torch only, any device):
+    ``chain`` int64[E] is the chain every entry reads and feeds, ``cnt`` int64[E] the bits it
+    leaves behind, ``emarket`` int64[E] its market (entries ascend by market).  Returns ``(qstart
+    [n_chains + 1], qpos, qentry, qlast [E, by entry], slast [n_chains])`` as there.  ``partial``:
+    entries with ``chain < 0`` are no queries (their ``qlast`` stays -1), so ``qpos`` / ``qentry``
+    are shorter than E."""
+    E, C = chain.numel(), int(n_chains)
+    dev = chain.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    if partial:
+        sel = torch.nonzero(chain >= 0).flatten()
+        chain = chain[sel]
+    skey, qentry = torch.sort(chain, stable=True)  # entries ascend by market: (chain, market) order
+    Q = qentry.numel()
+    qstart = torch.zeros(C + 1, **i64)
+    qstart[1:] = torch.cumsum(torch.bincount(chain, minlength=C), 0)
+    if partial:
+        qentry = sel[qentry]
     c = cnt[qentry]
     excl = torch.cumsum(c, 0) - c
-    first = qstart[skey]                       # the source's first query
-    qpos = excl - excl[first] if E else excl
-    # the last query before this one, in the same source, whose market left bits
-    at = torch.where(c > 0, torch.arange(E, **i64), torch.full((E,), -1, **i64))
-    incl = torch.cummax(at, 0).values if E else at
-    prev = torch.cat([torch.full((1,), -1, **i64), incl[:-1]]) if E else incl
+    first = qstart[skey]                       # the chain's first query
+    qpos = excl - excl[first] if Q else excl
+    # the last query before this one, in the same chain, whose market left bits
+    at = torch.where(c > 0, torch.arange(Q, **i64), torch.full((Q,), -1, **i64))
+    incl = torch.cummax(at, 0).values if Q else at
+    prev = torch.cat([torch.full((1,), -1, **i64), incl[:-1]]) if Q else incl
     has = prev >= first
     qm = emarket[qentry]
     qlast = torch.full((E,), -1, dtype=torch.int32, device=dev)
-    qlast[qentry] = torch.where(has, qm[prev.clamp(min=0)], torch.full((E,), -1, **i64)).to(torch.int32)
-    slast = torch.full((S,), -1, **i64)
+    qlast[qentry] = torch.where(has, qm[prev.clamp(min=0)], torch.full((Q,), -1, **i64)).to(torch.int32)
+    slast = torch.full((C,), -1, **i64)
     live = torch.nonzero(qstart[1:] > qstart[:-1]).flatten()
     if live.numel():
         end = incl[qstart[1:][live] - 1]
@@ -1686,6 +1718,277 @@ def settle_domains(plan: DomainPlan, domains: PairTable, offsets: torch.Tensor, 
         raise ValueError("outcome must have one entry per market of the plan")
     masked = torch.where(plan.market_domain.to(outcome.device) >= 0, outcome, torch.full_like(outcome, -1))
     return settle_pairs(plan, domains, offsets, prob, masked, now_us, **settle_kwargs)
+
+
+# ---------------------------------------------------------------------------------------
+# namespaced walk-forward: a domain per market, the fallback at every read
+# ---------------------------------------------------------------------------------------
+@dataclass
+class WalkQueries:
+    """The queries of one chain family of a :class:`WalkScopePlan`, as :class:`WalkPlan` holds
+    them for its single family: ``qstart`` int64[C+1], ``qpos`` int64[Q], ``qentry`` int32[Q],
+    ``qlast`` int32[E] (by entry, -1: no earlier bit, or the entry is no query of the family),
+    ``slast`` int64[C] (the last market that left a bit in the chain, -1: none)."""
+
+    qstart: torch.Tensor
+    qpos: torch.Tensor
+    qentry: torch.Tensor
+    qlast: torch.Tensor
+    slast: torch.Tensor
+
+
+def _global_outcome(outcome: torch.Tensor, market_domain: torch.Tensor, update_global: bool) -> torch.Tensor:
+    """The outcome as the global chains see it: every resolved market with ``update_global``,
+    else only those without a domain (reliability_abstraction.py:211-229)."""
+    if update_global:
+        return outcome
+    return torch.where(market_domain.to(outcome.device) < 0, outcome, torch.full_like(outcome, -1))
+
+
+@dataclass
+class WalkScopePlan:
+    """A chronological CSR batch whose markets belong to different domains, compiled for
+    :func:`walk_forward_scoped`.  ``pairs``: the :class:`PairPlan` over ALL markets (entries E);
+    ``dplan``: the :class:`DomainPlan` (chains F) and ``dentry`` int32[E], the domain chain of
+    every entry (-1: its market has no domain); ``dsettle`` / ``gsettle``: the
+    :class:`SettlePlan` of the domain chains (over the F entry space, as :func:`settle_domains`
+    compiles it) and of the global chains (over the S sources: the resolved markets without a
+    domain, or every resolved market with ``update_global``); ``dq`` / ``gq``: the
+    :class:`WalkQueries` of either family -- every entry is a query of its global chain, and of
+    its domain chain where ``dentry >= 0``.  ``n_clamped``: sids outside ``[0, n_sources)``."""
+
+    pairs: PairPlan
+    dplan: "DomainPlan"
+    dentry: torch.Tensor
+    dsettle: SettlePlan
+    gsettle: SettlePlan
+    dq: WalkQueries
+    gq: WalkQueries
+    update_global: bool
+    n_clamped: int
+
+    @classmethod
+    def order(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
+              market_domain: torch.Tensor, n_sources: int, n_domains: int, update_global: bool = False):
+        """The integer half of :meth:`build` (torch only, CPU tensors included): ``(pairs, dplan,
+        dentry, dq, gq, n_clamped)``.  Argument errors as :meth:`WalkPlan.order` and
+        :meth:`DomainPlan.build`."""
+        M = offsets.numel() - 1
+        try:
+            S = int(n_sources)
+        except (TypeError, ValueError):
+            raise ValueError(f"n_sources must be in [1, 2^31) (got {n_sources!r})") from None
+        if not 0 < S < (1 << 31):
+            raise ValueError(f"n_sources must be in [1, 2^31) (got {n_sources})")
+        if outcome.dtype != torch.int8:
+            raise ValueError(f"outcome must be int8 (-1 unresolved, 0, 1), got {outcome.dtype}")
+        if outcome.dim() != 1 or outcome.numel() != M:
+            raise ValueError(f"outcome must have one entry per market ({M}), got {tuple(outcome.shape)}")
+        clamped = sid.to(torch.int32).clamp(0, S - 1)
+        n_clamped = int((clamped != sid).sum())
+        dplan = DomainPlan.build(offsets, clamped, market_domain, S, n_domains)  # checks market_domain / offsets
+        pairs = PairPlan.build(offsets, clamped, prob, S)
+        E, F = pairs.n_entries, dplan.n_entries
+        usid = pairs.usid[:E].to(torch.int64)
+        emarket = pairs.emarket[:E].to(torch.int64)
+        edom = dplan.market_domain.to(torch.int64)[emarket]
+        # the (domain, source) keys of the DomainPlan ascend: the chain of an entry by search
+        fkey = dplan.emarket[:F].to(torch.int64) * S + dplan.usid[:F].to(torch.int64)
+        at = torch.searchsorted(fkey, edom.clamp(min=0) * S + usid) if F else torch.zeros_like(usid)
+        dentry = torch.where(edom >= 0, at, torch.full_like(at, -1))
+        signals = _entry_signals(pairs)
+        dq = WalkQueries(*_chain_queries(dentry, signals * (outcome[emarket] >= 0), emarket, max(F, 1),
+                                         partial=True))
+        gout = _global_outcome(outcome, dplan.market_domain, update_global)
+        gq = WalkQueries(*_chain_queries(usid, signals * (gout[emarket] >= 0), emarket, S))
+        return pairs, dplan, dentry.to(torch.int32), dq, gq, n_clamped
+
+    @classmethod
+    def build(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
+              market_domain: torch.Tensor, n_sources: int, n_domains: int, update_global: bool = False,
+              check: bool = True) -> "WalkScopePlan":
+        """Compile ``(offsets, sid, prob)`` in chronological market order with ``outcome``
+        int8[M] (-1 unresolved, 0, 1) and ``market_domain`` int32[M] (-1: none).  Torch sorts and
+        scans plus two :meth:`SettlePlan.build`; synchronises.  A ``sid`` outside ``[0,
+        n_sources)`` is clamped and raises :class:`BCEError` (``check=False``: the fault is left
+        for :func:`walk_forward_scoped`)."""
+        update_global = bool(update_global)
+        pairs, dplan, dentry, dq, gq, n_clamped = cls.order(offsets, sid, prob, outcome, market_domain, n_sources,
+                                                            n_domains, update_global)
+        masked = torch.where(dplan.market_domain >= 0, outcome, torch.full_like(outcome, -1))
+        dsettle = SettlePlan.build(offsets, dplan.esid, prob, masked, max(dplan.n_entries, 1), check=check)
+        gsettle = SettlePlan.build(offsets, sid, prob, _global_outcome(outcome, dplan.market_domain, update_global),
+                                   n_sources, check=check)
+        if check and n_clamped:  # in a market that feeds no global chain: the compile does not see it
+            raise N.BCEError(f"walk scope plan: {n_clamped} sid outside [0, {int(n_sources)})")
+        return cls(pairs, dplan, dentry, dsettle, gsettle, dq, gq, update_global, n_clamped)
+
+
+@dataclass
+class WalkScopeResult:
+    """:func:`walk_forward_scoped`: ``result`` is the batch's :class:`ConsensusResult` (its
+    fields are reachable directly; ``usid`` holds the ENTRY index | cold << 31); ``scope`` u8[E]
+    the NS_* code every entry was read at; ``domains`` the NEW domain table (the input one where
+    nothing was committed); ``domain_total`` / ``domain_correct`` int64[F] and ``global_total`` /
+    ``global_correct`` int64[S]: the chain lengths and their set bits per family."""
+
+    result: ConsensusResult
+    plan: WalkScopePlan
+    scope: torch.Tensor
+    domains: PairTable
+    domain_total: torch.Tensor
+    domain_correct: torch.Tensor
+    global_total: torch.Tensor
+    global_correct: torch.Tensor
+
+    __getattr__ = WalkResult.__getattr__
+    is_null = WalkResult.is_null
+
+
+def _walk_scope_read(plan: WalkScopePlan, domains: PairTable, global_table: Optional["ReliabilityTable"],
+                     market_time_us: torch.Tensor, pairs: Optional[PairTable], global_has: Optional[torch.Tensor],
+                     mark_cold: bool, long_min: Optional[int], chunk_bits: Optional[int], half_life_days: float,
+                     min_rel: float):
+    """The launches of :func:`walk_scope_trace`; also returns the raw start rows of the domain
+    chains (:func:`pair_resolve`, None without one) and the ``has`` flags of the global table."""
+    L = N.require_gpu()
+    pp, dp = plan.pairs, plan.dplan
+    S, E, M, F = pp.n_sources, pp.n_entries, pp.n_markets, dp.n_entries
+    if domains.n_markets != dp.n_markets or domains.n_sources != S:
+        raise ValueError("the plan and the domain table describe different batches")
+    if pairs is not None and (pairs.n_markets != M or pairs.n_sources != S):
+        raise ValueError("the plan and the pair table describe different batches")
+    if market_time_us.dtype != torch.int64 or market_time_us.dim() != 1 or market_time_us.numel() != M:
+        raise ValueError(f"market_time_us must be int64 with one entry per market ({M})")
+    g = global_table
+    if g is None and plan.gsettle.n_touched:
+        raise ValueError("the batch updates the global scope: global_table is needed")
+    if g is not None:
+        assert g.rel.dtype == torch.float64 and g.conf.dtype == torch.float64 and g.t_us.dtype == torch.int64, \
+            "rel / conf must be fp64 and t_us int64"
+        assert g.rel.numel() == S and g.conf.numel() == S and g.t_us.numel() == S, \
+            "the global table must have n_sources rows"
+        assert g.present is None or (g.present.dtype == torch.uint8 and g.present.numel() == S), \
+            "present must be u8[n_sources]"
+        if global_has is None:
+            global_has = g.present if g.present is not None else torch.ones(S, dtype=torch.uint8,
+                                                                           device=g.rel.device)
+        assert global_has.dtype == torch.uint8 and global_has.numel() == S, "global_has must be u8[n_sources]"
+    long_min = WALK_LONG_MIN if long_min is None else long_min
+    chunk_bits = WALK_CHUNK_BITS if chunk_bits is None else chunk_bits
+    dev = pp.esid.device
+    st = N.stream(dev)
+    E1 = max(E, 1)
+    relconf = torch.empty((E1, 2), dtype=torch.float64, device=dev)  # the global trace, overwritten in place
+    bits = torch.zeros(max((E + 31) // 32, 1), dtype=torch.int32, device=dev)
+    scope = torch.empty(E1, dtype=torch.uint8, device=dev)
+    mtime = market_time_us.contiguous()
+    ent = lambda t: N.ptr(t if E else None)  # noqa: E731
+
+    def trace(sp, q, rel, conf, present, out):
+        n_long, chunk_start, n_chunks = sp.chunks(long_min, chunk_bits)
+        N.check(L.bce_settle_trace(N.ptr(sp.bits), sp.n_bits, N.ptr(sp.start), N.ptr(sp.order), sp.n_touched, n_long,
+                                   N.ptr(chunk_start), n_chunks, int(chunk_bits), sp.n_sources, N.ptr(rel),
+                                   N.ptr(conf), N.ptr(present), DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE,
+                                   N.ptr(q.qstart), ent(q.qpos), ent(q.qentry), E, N.ptr(out), st),
+                "bce_settle_trace")
+
+    raw = dhas = dtrace = None
+    if F and E:  # the domain chains: start rows by the raw pair lookup over the (domain, source) entries
+        raw = pair_resolve(dp.uoffsets, dp.usid, domains, 0, mode="raw", emarket=dp.emarket)
+        R = domains.n_rows
+        dhas = (raw.matched & domains.has[raw.lb.clamp(max=R - 1)]) if R else torch.zeros_like(raw.matched)
+        dtrace = torch.empty((E1, 2), dtype=torch.float64, device=dev)
+        if plan.dsettle.n_touched:
+            trace(plan.dsettle, plan.dq, raw.rel, raw.conf, raw.present, dtrace)
+    gtraced = g is not None and plan.gsettle.n_touched > 0
+    if gtraced:
+        trace(plan.gsettle, plan.gq, g.rel, g.conf, g.present, relconf)
+    dom = [N.ptr(x) for x in ((plan.dentry, plan.dq.qlast, dtrace, raw.rel, raw.conf, raw.t_us, dhas)
+                              if raw is not None else (None,) * 7)]
+    glo = [N.ptr(x) for x in ((plan.gq.qlast if gtraced else None, relconf if gtraced else None, g.rel, g.conf,
+                               g.t_us, global_has.contiguous()) if g is not None else (None,) * 6)]
+    N.check(L.bce_walk_scope_read(E, ent(pp.usid), ent(pp.emarket), N.ptr(mtime if M else None), M, S,
+                                  N.ptr(pairs.poffsets if pairs is not None else None), *_pair_pointers(pairs),
+                                  pairs.n_rows if pairs is not None else 0, *dom, F if raw is not None else 0, *glo,
+                                  float(half_life_days), float(min_rel), DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE,
+                                  int(bool(mark_cold)), int(plan.n_clamped > 0), N.ptr(relconf), N.ptr(bits),
+                                  N.ptr(scope), st), "bce_walk_scope_read")
+    return SourceTable(relconf, bits, range(E)), scope[:E], raw, global_has  # "names": the entry indices
+
+
+def walk_scope_trace(plan: WalkScopePlan, domains: PairTable, global_table: Optional["ReliabilityTable"],
+                     market_time_us: torch.Tensor, *, pairs: Optional[PairTable] = None,
+                     global_has: Optional[torch.Tensor] = None, mark_cold: bool = False,
+                     long_min: Optional[int] = None, chunk_bits: Optional[int] = None,
+                     half_life_days: float = DECAY_HALF_LIFE_DAYS, min_rel: float = DECAY_MINIMUM):
+    """The read side of :func:`walk_forward_scoped` alone: one bce_settle_trace per chain family
+    that has bits (the domain chains from the raw :func:`pair_resolve` rows of ``plan.dplan``, the
+    global chains from the dense table), then bce_walk_scope_read.  Returns the consensus table
+    over the entry index -- every entry's namespaced ``get_reliability(apply_decay=True)`` at its
+    market's time, after the earlier markets were settled -- and ``scope`` u8[E] (NS_* codes).
+    No table is written."""
+    return _walk_scope_read(plan, domains, global_table, market_time_us, pairs, global_has, mark_cold, long_min,
+                            chunk_bits, half_life_days, min_rel)[:2]
+
+
+def walk_forward_scoped(plan: WalkScopePlan, domains: PairTable, global_table: Optional["ReliabilityTable"],
+                        market_time_us: torch.Tensor, *, offsets: torch.Tensor, prob: torch.Tensor,
+                        pairs: Optional[PairTable] = None, global_has: Optional[torch.Tensor] = None,
+                        mark_cold: bool = False, mode: str = "exact", long_min: Optional[int] = None,
+                        chunk_bits: Optional[int] = None, commit: bool = True,
+                        **consensus_kwargs) -> WalkScopeResult:
+    """:func:`walk_forward` over NamespacedReliabilityStore, bit-exact: for m = 0..M-1, market m
+    is scored by compute_consensus with every source fetched by ``get_reliability(s, market_id,
+    domain_of(m), apply_decay=True)`` with the clock at ``market_time_us[m]`` -- the first of the
+    market row, the domain row, the global row whose ``updated_at`` is truthy AT THAT TURN, else
+    the cold start (reliability_abstraction.py:119-188) -- and then, if ``outcome[m] >= 0``,
+    ``update_reliability(s, correct, domain=domain_of(m), update_global=plan.update_global)`` runs
+    per signal in position order (:190-239) and stamps the rows it writes with that time.
+
+    ``domains``: the sparse rows of the D domains (a :class:`PairTable` over the domain index; a
+    row whose ``has`` is 0 is skipped by reads but is the start of its chain); ``global_table``:
+    the dense global scope, ``present`` = a row exists, with ``global_has`` u8[S] = its
+    ``updated_at`` is truthy (default: ``present``); None = the scope is not requested, which a
+    batch that updates it refuses with ``ValueError``.  ``pairs``: the market-scope rows of the
+    batch's markets (read only; None = ``market_id=None``).  ``mark_cold`` sets the cold bit of
+    ``usid`` where the read ended at the cold start.
+
+    :func:`walk_scope_trace` builds the consensus table over the entries, :func:`consensus` runs
+    unchanged with ``plan.pairs.esid`` as the ranks (``mode`` and ``consensus_kwargs`` go to it;
+    ``bins=`` is its length-bin :class:`Plan`).  ``commit=True``: the domain chains are settled on
+    their raw start rows, stamped with the time of each chain's last market and merged into a NEW
+    :class:`PairTable` (``result.domains``; ``domains`` itself is never written); the global table
+    is settled in place as :func:`walk_forward` leaves it, ``global_has`` set for the touched
+    sources.  ``commit=False`` leaves every input untouched.  The result does not depend on
+    ``long_min`` / ``chunk_bits``."""
+    pp = plan.pairs
+    if offsets.numel() - 1 != pp.n_markets or prob.numel() != pp.esid.numel():
+        raise ValueError("offsets / prob are not the batch the plan was built from")
+    wtable, scope, raw, ghas = _walk_scope_read(plan, domains, global_table, market_time_us, pairs, global_has,
+                                                mark_cold, long_min, chunk_bits, DECAY_HALF_LIFE_DAYS, DECAY_MINIMUM)
+    res = consensus(offsets, pp.esid, prob.to(torch.float64), wtable, mode=mode, **_bins_as_plan(consensus_kwargs))
+    ds, gs = plan.dsettle, plan.gsettle
+    new_domains = domains
+    if commit:
+        kw = {}
+        if long_min is not None:
+            kw["long_min"] = long_min
+        if chunk_bits is not None:
+            kw["chunk_bits"] = chunk_bits
+        if ds.n_touched and raw is not None:
+            settle(ds, raw.rel, raw.conf, raw.t_us, raw.present, 0, **kw)
+            touched = ds.order.to(torch.int64)
+            raw.t_us.index_copy_(0, touched, market_time_us[plan.dq.slast[touched]])
+            new_domains = _pair_merge(plan.dplan, domains, raw, ds.total[:plan.dplan.n_entries] > 0)
+        if gs.n_touched:
+            g = global_table
+            settle(gs, g.rel, g.conf, g.t_us, g.present, 0, **kw)
+            touched = gs.order.to(torch.int64)
+            g.t_us.index_copy_(0, touched, market_time_us[plan.gq.slast[touched]])
+            if ghas is not g.present:
+                ghas.index_fill_(0, touched, 1)
+    return WalkScopeResult(res, plan, scope, new_domains, ds.total, ds.correct, gs.total, gs.correct)
 
 
 # ---------------------------------------------------------------------------------------

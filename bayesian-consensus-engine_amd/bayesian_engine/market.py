@@ -477,7 +477,8 @@ class CrossMarketAggregator:
                                     update_global=update_global, dry_run=dry_run)
 
     def walk_forward(self, store, patterns: Optional[List[str]] = None, domain: Optional[str] = None,
-                     dry_run: bool = False, device_match: Optional[bool] = None):
+                     dry_run: bool = False, device_match: Optional[bool] = None, domain_of=None,
+                     update_global: bool = False, market_scope: bool = False):
         """A back-test over the store's history: every market with signals (selected as
         reestimate_sources selects them), ordered by (time, store position) -- ``resolved_at`` for
         a RESOLVED market with an outcome, ``created_at`` otherwise -- is scored with the
@@ -485,7 +486,18 @@ class CrossMarketAggregator:
         own time, then settled itself if it is resolved; unresolved markets read and commit
         nothing (``store.walk_forward``, :class:`NamespacedReliabilityStore`).  Returns
         ``(results, summary)``: the consensus dict of every market keyed by ``str(market.id)``, in
-        walk order, and the store's settle summary."""
+        walk order, and the store's settle summary.
+
+        ``domain_of`` (as in ``settle_resolved``; together with ``domain=``, ``ValueError``) walks
+        a history that spans domains: every market is read with the fallback market -> domain ->
+        global -> cold start and settled at the scope of its own domain, ``update_global`` as
+        ``update_reliability`` takes it (``store.walk_forward_namespaced``); ``market_scope=True``
+        passes ``str(market.id)`` so that seeded (source, market) rows are read first.  Without
+        ``domain_of`` the two flags are not used."""
+        if domain_of is not None:
+            if domain is not None:
+                raise ValueError("domain= (one for the batch) and domain_of= (one per market) exclude each other")
+            domain_of = _domain_fn(domain_of)
         markets = self._select(None, patterns, device_match, with_signals=True)
         keyed = []
         for pos, m in enumerate(markets):
@@ -497,8 +509,14 @@ class CrossMarketAggregator:
             keyed.append((t, pos, m, resolved))
         keyed.sort(key=lambda k: k[:2])
         batch_markets = [(m.signals, m.outcome if resolved else None) for _, _, m, resolved in keyed]
-        results, summary = store.walk_forward(batch_markets, [us_to_iso(t) for t, _, _, _ in keyed], domain=domain,
-                                              dry_run=dry_run)
+        stamps = [us_to_iso(t) for t, _, _, _ in keyed]
+        if domain_of is not None:
+            results, summary = store.walk_forward_namespaced(
+                batch_markets, stamps, domains=[domain_of(m) for _, _, m, _ in keyed],
+                market_ids=[str(m.id) for _, _, m, _ in keyed] if market_scope else None,
+                update_global=update_global, dry_run=dry_run)
+        else:
+            results, summary = store.walk_forward(batch_markets, stamps, domain=domain, dry_run=dry_run)
         out = {}
         for (_, _, m, _), r in zip(keyed, results):
             r["marketId"] = str(m.id)

@@ -19,6 +19,7 @@ from enum import Enum
 from typing import List, Optional, Protocol, Sequence, Tuple, runtime_checkable
 
 import numpy as np
+import torch
 
 from . import _native as N
 from . import batch
@@ -85,6 +86,39 @@ def _namespaced(r, namespace: ReliabilityNamespace, value: str) -> NamespacedRel
 def _outcome_codes(markets) -> np.ndarray:
     """int8 per ``(signals, outcome)``: -1 unresolved (None), else the outcome's truth."""
     return np.array([-1 if o is None else (1 if o else 0) for _, o in markets], np.int8)
+
+
+def _walk_dicts(markets, offsets, names, res, pairs) -> list:
+    """The per-market ``compute_consensus``-shaped dicts of a walk-forward result whose ``usid``
+    holds entry indices of ``pairs``."""
+    cons, confd, tot = (x.cpu().numpy() for x in (res.consensus, res.confidence, res.total_weight))
+    n_unique, usid = res.n_unique.cpu().numpy(), res.usid.cpu().numpy()
+    weight, nweight = res.weight.cpu().numpy(), res.nweight.cpu().numpy()
+    esrc = pairs.usid.cpu().numpy()
+    results = []
+    for m, (signals, _) in enumerate(markets):
+        if not signals:
+            results.append(core_no_signals())
+            continue
+        a, b = offsets[m], offsets[m] + int(n_unique[m])
+        ids = [names[esrc[e & 0x7FFFFFFF]] for e in usid[a:b]]
+        results.append(consensus_dict(ids, weight[a:b], nweight[a:b], cons[m], confd[m], tot[m], len(signals),
+                                      []))  # every source was fetched: none is cold
+    return results
+
+
+def _domain_counts(domains, markets):
+    """summarize_sources' ``total`` / ``correct`` keyed ``(source_id, domain-or-None)``."""
+    total: dict = {}
+    correct: dict = {}
+    for d, (signals, out) in zip(domains, markets):
+        if out is None:
+            continue
+        for s in signals:
+            k = (s["sourceId"], d if d else None)
+            total[k] = total.get(k, 0) + 1
+            correct[k] = correct.get(k, 0) + int((s.get("probability", 0.5) >= 0.5) == bool(out))
+    return total, correct
 
 
 # scope code (bce_namespace_resolve) -> (namespace, is_fallback)
@@ -333,15 +367,7 @@ class NamespacedReliabilityStore:
         if bool((gout >= 0).any()):
             gplan = batch.SettlePlan.build(T(offsets), T(sid), T(prob), T(gout), len(names))
             global_records = self._settle_global(names, gplan, dry_run, now)
-        total: dict = {}
-        correct: dict = {}
-        for d, (signals, out) in zip(domains, markets):
-            if out is None:
-                continue
-            for s in signals:
-                k = (s["sourceId"], d if d else None)
-                total[k] = total.get(k, 0) + 1
-                correct[k] = correct.get(k, 0) + int((s.get("probability", 0.5) >= 0.5) == bool(out))
+        total, correct = _domain_counts(domains, markets)
         for k in total:
             if k[1] is None:
                 records[k] = global_records[k[0]]
@@ -382,19 +408,7 @@ class NamespacedReliabilityStore:
         table = self._store.load_table(target, names, device=dev)
         res = table.walk_forward(plan, T(t_us), offsets=off, prob=prob, validate=False)
         N.check_faults(dev, "walk_forward")
-        cons, confd, tot = (x.cpu().numpy() for x in (res.consensus, res.confidence, res.total_weight))
-        n_unique, usid = res.n_unique.cpu().numpy(), res.usid.cpu().numpy()
-        weight, nweight = res.weight.cpu().numpy(), res.nweight.cpu().numpy()
-        esrc = plan.pairs.usid.cpu().numpy()
-        results = []
-        for m, (signals, _) in enumerate(markets):
-            if not signals:
-                results.append(core_no_signals())
-                continue
-            a, b = offsets[m], offsets[m] + int(n_unique[m])
-            ids = [names[esrc[e & 0x7FFFFFFF]] for e in usid[a:b]]
-            results.append(consensus_dict(ids, weight[a:b], nweight[a:b], cons[m], confd[m], tot[m], len(signals),
-                                          []))  # every source was fetched: none is cold
+        results = _walk_dicts(markets, offsets, names, res, plan.pairs)
         touched = sorted(int(x) for x in plan.settle.order.cpu().numpy())
         rel, conf, stamp_us = table.rel.cpu().numpy(), table.conf.cpu().numpy(), table.t_us.cpu().numpy()
         total, correct = plan.total.cpu().numpy(), plan.correct.cpu().numpy()
@@ -405,6 +419,97 @@ class NamespacedReliabilityStore:
                                 for r in records.values())
         return results, SettleSummary(records, {}, {names[i]: int(total[i]) for i in touched},
                                       {names[i]: int(correct[i]) for i in touched})
+
+    def walk_forward_namespaced(self, markets: Sequence[tuple], times: Sequence, domains=None,
+                                market_ids: Optional[Sequence[str]] = None, update_global: bool = False,
+                                dry_run: bool = False):
+        """:meth:`walk_forward` for a history that spans domains, with the fallback chain at
+        every read, as ONE compiled batch (:func:`batch.walk_forward_scoped`): market i is scored
+        by ``compute_consensus`` with every source fetched by ``get_reliability(sid,
+        market_id=market_ids[i], domain=domains[i], apply_decay=True)`` at ``times[i]``, then, if
+        its outcome is not None, ``update_reliability(sid, correct, domain=domains[i],
+        update_global=update_global)`` runs for every signal and stamps the rows it writes with
+        ``times[i]``.  ``domains`` is one entry per market (falsy = none) or one string for all;
+        ``market_ids`` (optional, truthy and distinct, else ``ValueError``) are used for the read
+        only: market-scope rows are priors and are not settled here.  Sources are interned in
+        sorted() order and domains in first-seen order; the market and domain rows are loaded
+        with ``load_pair_table``, ``__global__`` with ``load_table``, and the touched domain and
+        global rows written back with one ``executemany``, each with its own ``updated_at``,
+        unless ``dry_run``.  Returns ``(results, summary)``: one dict per market shaped like
+        ``compute_consensus``'s, and a :class:`SettleSummary` keyed as
+        ``settle_markets(domains=)`` keys it (``(source_id, domain-or-None)``)."""
+        markets = [(list(signals), outcome) for signals, outcome in markets]
+        times = list(times)
+        M = len(markets)
+        if len(times) != M:
+            raise ValueError(f"times has {len(times)} entries for {M} markets")
+        t_us = np.array([iso_to_us(t) if isinstance(t, str) else dt_to_us(t) for t in times], np.int64)
+        if (t_us == NO_TIMESTAMP).any():
+            raise ValueError("a market time is empty or unparseable")
+        domains = [domains] * M if isinstance(domains, str) or domains is None else list(domains)
+        if len(domains) != M:
+            raise ValueError(f"domains has {len(domains)} entries for {M} markets")
+        if market_ids is not None:
+            market_ids = [str(m) for m in market_ids]
+            if len(market_ids) != M:
+                raise ValueError(f"market_ids has {len(market_ids)} entries for {M} markets")
+            if not all(market_ids):
+                raise ValueError("every market id must be truthy (a falsy one selects another scope)")
+            if len(set(market_ids)) != M:
+                raise ValueError("duplicate market id in market_ids")
+        rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
+        names = list(rank)
+        offsets, sid, prob = signals_csr([signals for signals, _ in markets], rank)
+        outcome = _outcome_codes(markets)
+        if not names:
+            return [core_no_signals() for _ in markets], SettleSummary({}, {}, {}, {})
+        dnames = list(dict.fromkeys(d for d in domains if d))
+        drank = {d: i for i, d in enumerate(dnames)}
+        market_domain = np.array([drank[d] if d else -1 for d in domains], np.int32)
+        N.require_gpu()
+        dev = N.device()
+        T = batch.to_device(dev)
+        off, prob = T(offsets), T(prob)
+        plan = batch.WalkScopePlan.build(off, T(sid), prob, T(outcome), T(market_domain), len(names), len(dnames),
+                                         update_global=update_global)
+        dkeys = [f"__domain__:{d}" for d in dnames]
+        dtable = self._store.load_pair_table(dkeys, names, device=dev)
+        ptable = self._store.load_pair_table(market_ids, names, device=dev) if market_ids is not None else None
+        gtable = self._store.load_table(self.GLOBAL_MARKET_ID, names, device=dev)
+        stamps = self._store.fetch_pairs([(n, self.GLOBAL_MARKET_ID) for n in names])
+        ghas = T(np.array([1 if stamps.get((n, self.GLOBAL_MARKET_ID), (0, 0, ""))[2] else 0 for n in names],
+                          np.uint8))
+        res = batch.walk_forward_scoped(plan, dtable, gtable, T(t_us), offsets=off, prob=prob, pairs=ptable,
+                                        global_has=ghas, validate=False)
+        N.check_faults(dev, "walk_forward_namespaced")
+        results = _walk_dicts(markets, offsets, names, res, plan.pairs)
+        records, global_records, rows = {}, {}, []
+        F = plan.dplan.n_entries
+        if F and plan.dsettle.n_touched:  # every touched chain has a row in the new table: read them back
+            r = batch.pair_resolve(plan.dplan.uoffsets, plan.dplan.usid, res.domains, 0, mode="raw",
+                                   emarket=plan.dplan.emarket)
+            touched = torch.nonzero(res.domain_total[:F] > 0).flatten()
+            cols = [x[touched].cpu().numpy() for x in (plan.dplan.emarket, plan.dplan.usid, r.rel, r.conf, r.t_us)]
+            for d, s, x, c, t in zip(*cols):
+                rec = NamespacedReliabilityRecord(names[int(s)], ReliabilityNamespace.DOMAIN, dnames[int(d)],
+                                                  float(x), float(c), us_to_iso(int(t)), False)
+                records[(rec.source_id, rec.namespace_value)] = rec
+                rows.append((rec.source_id, dkeys[int(d)], rec.reliability, rec.confidence, rec.updated_at))
+        gtouched = sorted(int(x) for x in plan.gsettle.order.cpu().numpy())
+        rel, conf, stamp_us = gtable.rel.cpu().numpy(), gtable.conf.cpu().numpy(), gtable.t_us.cpu().numpy()
+        for i in gtouched:
+            rec = NamespacedReliabilityRecord(names[i], ReliabilityNamespace.GLOBAL, "global", float(rel[i]),
+                                              float(conf[i]), us_to_iso(int(stamp_us[i])), False)
+            global_records[names[i]] = rec
+            rows.append((rec.source_id, self.GLOBAL_MARKET_ID, rec.reliability, rec.confidence, rec.updated_at))
+        N.check_faults(dev, "walk_forward_namespaced")
+        total, correct = _domain_counts(domains, markets)
+        for k in total:
+            if k[1] is None:
+                records[k] = global_records[k[0]]
+        if not dry_run and rows:
+            self._store._upsert(rows)
+        return results, SettleSummary(records, global_records, total, correct)
 
     def get_reliability_many(self, names: Sequence[str], market_id: Optional[str] = None,
                              domain: Optional[str] = None, apply_decay: bool = True,

@@ -469,6 +469,48 @@ int bce_walk_read(int64_t n_entries, const int32_t* usid, const int32_t* emarket
                   int mark_cold, int sid_clamped, double* relconf, uint32_t* present_bits, uint8_t* exists,
                   void* stream);
 
+/* ---- namespaced walk-forward: the market -> domain -> global fallback at every read ----------
+ * The walk above with NamespacedReliabilityStore in the store's place: market m fetches every
+ * source with get_reliability(s, market_id, domain_of(m), apply_decay=True)
+ * (reliability_abstraction.py:119-188) at market_time_us[m], and a resolved market then runs
+ * update_reliability(s, correct, domain=domain_of(m), update_global=) per signal (:190-239), which
+ * writes the domain row (the global row for a market without a domain) and, with update_global,
+ * the global row as well.  Two chain families are traced by bce_settle_trace, each into a buffer
+ * of its own over the entry index: the (domain, source) chains (n_dentries chain ids; dentry
+ * [n_entries] = the chain of every entry, -1 = its market has no domain) and the per-source global
+ * chains.  Market rows (the table of bce_pair_resolve) are read only.
+ *
+ * bce_walk_scope_read: per entry e of market m = emarket[e] and source s = usid[e], the first of
+ *   1. the market row of (m, s) where it exists and phas (poffsets NULL: no market scope);
+ *   2. with f = dentry[e] >= 0: dtrace[e] stamped with market_time_us[dqlast[e]] where
+ *      dqlast[e] >= 0, else the start row f of drel / dconf / dt_us where dhas[f] (dentry NULL:
+ *      no domain scope);
+ *   3. gtrace[e] stamped with market_time_us[gqlast[e]] where gqlast[e] >= 0, else the dense
+ *      start row s of grel / gconf / gt_us where ghas[s] (grel NULL: the scope is not requested;
+ *      gqlast NULL: no global chain has a bit);
+ *   4. (default_rel, default_conf), undecayed.
+ * A chain with a bit before the entry's market has a truthy stamp whatever its start row was;
+ * dhas / ghas are "updated_at is truthy" of the start rows (the start STATE of a chain is the
+ * row where it exists at all: that is bce_settle_trace's `present`).  The picked state is decayed
+ * from its stamp to market_time_us[m] (equal or earlier times, BCE_NO_TIMESTAMP: no decay).
+ * Outputs: relconf[2 * n_entries] (16-byte aligned; may be dtrace or gtrace itself: entry e reads
+ * only element e of either, before it stores), present_bits[ceil(n_entries / 32)] (all set, or
+ * with mark_cold only where scope != 3) and scope[n_entries] (0 / 1 / 2 / 3).
+ * No input makes the kernel read or write outside its arrays: an emarket, dqlast or gqlast outside
+ * the batch (read as market 0 / "no earlier bit"), a dentry outside [-1, n_dentries) (read as -1)
+ * and market-row offsets that are no segment of [0, n_rows] (searched as empty) raise the fault
+ * word; a usid outside [0, n_sources) is clamped and raises it, as does sid_clamped != 0. */
+int bce_walk_scope_read(int64_t n_entries, const int32_t* usid, const int32_t* emarket,
+                        const int64_t* market_time_us, int64_t n_markets, int32_t n_sources,
+                        const int64_t* poffsets, const int32_t* psid, const double* prel, const double* pconf,
+                        const int64_t* pt_us, const uint8_t* phas, int64_t n_rows, const int32_t* dentry,
+                        const int32_t* dqlast, const double* dtrace, const double* drel, const double* dconf,
+                        const int64_t* dt_us, const uint8_t* dhas, int64_t n_dentries, const int32_t* gqlast,
+                        const double* gtrace, const double* grel, const double* gconf, const int64_t* gt_us,
+                        const uint8_t* ghas, double half_life_days, double min_rel, double default_rel,
+                        double default_conf, int mark_cold, int sid_clamped, double* relconf,
+                        uint32_t* present_bits, uint8_t* scope, void* stream);
+
 /* ---- market-scope rows: the (source, market) rows of the store, looked up per pair ----------
  * Replaces, for every unique (market, source) pair of a batch, one call of
  *   BCE_PAIR_STORE       SQLiteReliabilityStore.get_reliability(sid, market_id, apply_decay)
