@@ -40,7 +40,8 @@ from .reliability_abstraction import NamespacedReliabilityStore
 from . import decay as _decay
 from .timeutil import NO_TIMESTAMP, dt_to_us, iso_to_us, us_to_iso
 
-__all__ = ["MarketId", "MarketStatus", "Market", "MarketStore", "SourcePerformance", "CrossMarketAggregator"]
+__all__ = ["MarketId", "MarketStatus", "Market", "MarketStore", "SourcePerformance", "BacktestScore", "SourceScore",
+           "WalkScore", "CrossMarketAggregator"]
 
 # device_match=None: (markets) x (patterns) from which the pattern filters take the GPU route when
 # a GPU is visible.  Measured crossover (tools/bench_glob.py part (e), name table cached): the
@@ -346,6 +347,75 @@ class SourcePerformance:
         return self.correct_predictions / total
 
 
+@dataclass
+class BacktestScore:
+    """The forecasts of one group of markets against their outcomes (``score_walk`` /
+    ``sweep_decay``): ``n`` scored markets, mean Brier score, mean log loss, accuracy of the
+    ``>= 0.5`` vote and expected calibration error (None where ``n == 0``); ``calibration`` one row
+    per non-empty bin: ``{"bin", "lo", "hi", "n", "mean_forecast", "observed"}``; the markets
+    left out are counted in ``n_unresolved`` / ``n_null`` (no consensus) / ``n_bad`` (a forecast
+    outside [0, 1]).  ``params``: the grid point of a sweep."""
+
+    n: int
+    brier: Optional[float]
+    log_loss: Optional[float]
+    accuracy: Optional[float]
+    ece: Optional[float]
+    calibration: List[Dict[str, Any]] = field(default_factory=list)
+    n_unresolved: int = 0
+    n_null: int = 0
+    n_bad: int = 0
+    params: Optional[Dict[str, float]] = None
+
+    @classmethod
+    def empty(cls, n_bins: int, params: Optional[Dict[str, float]] = None) -> "BacktestScore":
+        return cls(0, None, None, None, None, [], 0, 0, 0, params)
+
+    @classmethod
+    def from_result(cls, r: "batch.ScoreResult") -> List["BacktestScore"]:
+        """One per group of a 2-D :class:`batch.ScoreResult`."""
+        counts = r.counts.cpu().numpy()
+        brier, ll, acc, ece = (x.cpu().numpy() for x in (r.brier, r.log_loss, r.accuracy, r.ece))
+        mean, obs = (x.cpu().numpy() for x in r.calibration)
+        bin_n = r.bin_n.cpu().numpy()
+        B = bin_n.shape[1]
+        out = []
+        for g in range(counts.shape[0]):
+            n = int(counts[g, 0])
+            rows = [{"bin": b, "lo": b / B, "hi": (b + 1) / B, "n": int(bin_n[g, b]),
+                     "mean_forecast": float(mean[g, b]), "observed": float(obs[g, b])}
+                    for b in range(B) if bin_n[g, b]]
+            val = lambda x: float(x[g]) if n else None  # noqa: E731
+            out.append(cls(n, val(brier), val(ll), val(acc), val(ece), rows, int(counts[g, 2]), int(counts[g, 3]),
+                           int(counts[g, 4])))
+        return out
+
+
+@dataclass
+class SourceScore:
+    """One source's own signals against the outcomes (``score_walk(sources=True)``): ``n`` scored
+    signals, mean Brier score, mean log loss, accuracy, and ``skill`` = its Brier score minus the
+    consensus's over the same signals (negative: better than the consensus); NaN where n == 0."""
+
+    source_id: str
+    n: int
+    brier: float
+    log_loss: float
+    accuracy: float
+    skill: float
+
+
+@dataclass
+class WalkScore:
+    """``CrossMarketAggregator.score_walk``: the whole history, one score per pattern list, per
+    domain, and per source."""
+
+    overall: BacktestScore
+    groups: List[BacktestScore]
+    domains: Dict[str, BacktestScore]
+    sources: Dict[str, SourceScore]
+
+
 class CrossMarketAggregator:
     """Aggregate data across multiple markets (market.py:244-408)."""
 
@@ -498,18 +568,7 @@ class CrossMarketAggregator:
             if domain is not None:
                 raise ValueError("domain= (one for the batch) and domain_of= (one per market) exclude each other")
             domain_of = _domain_fn(domain_of)
-        markets = self._select(None, patterns, device_match, with_signals=True)
-        keyed = []
-        for pos, m in enumerate(markets):
-            resolved = m.status == MarketStatus.RESOLVED and m.outcome is not None
-            stamp = m.resolved_at if resolved and m.resolved_at else m.created_at
-            t = iso_to_us(stamp)
-            if t == NO_TIMESTAMP:
-                raise ValueError(f"market {m.id}: no usable time ({stamp!r})")
-            keyed.append((t, pos, m, resolved))
-        keyed.sort(key=lambda k: k[:2])
-        batch_markets = [(m.signals, m.outcome if resolved else None) for _, _, m, resolved in keyed]
-        stamps = [us_to_iso(t) for t, _, _, _ in keyed]
+        keyed, batch_markets, stamps = self._walk_history(patterns, device_match)
         if domain_of is not None:
             results, summary = store.walk_forward_namespaced(
                 batch_markets, stamps, domains=[domain_of(m) for _, _, m, _ in keyed],
@@ -522,6 +581,163 @@ class CrossMarketAggregator:
             r["marketId"] = str(m.id)
             out[str(m.id)] = r
         return out, summary
+
+    def _walk_history(self, patterns: Optional[List[str]], device_match: Optional[bool]):
+        """The markets of a back-test in walk order: ``(keyed, batch_markets, stamps)`` with
+        ``keyed`` = ``(time_us, store position, market, resolved)`` sorted by (time, position),
+        ``batch_markets`` the ``(signals, outcome or None)`` pairs and ``stamps`` the ISO times."""
+        markets = self._select(None, patterns, device_match, with_signals=True)
+        keyed = []
+        for pos, m in enumerate(markets):
+            resolved = m.status == MarketStatus.RESOLVED and m.outcome is not None
+            stamp = m.resolved_at if resolved and m.resolved_at else m.created_at
+            t = iso_to_us(stamp)
+            if t == NO_TIMESTAMP:
+                raise ValueError(f"market {m.id}: no usable time ({stamp!r})")
+            keyed.append((t, pos, m, resolved))
+        keyed.sort(key=lambda k: k[:2])
+        batch_markets = [(m.signals, m.outcome if resolved else None) for _, _, m, resolved in keyed]
+        stamps = [us_to_iso(t) for t, _, _, _ in keyed]
+        return keyed, batch_markets, stamps
+
+    def score_walk(self, results: Dict[str, Dict[str, Any]], pattern_lists: Optional[List[List[str]]] = None,
+                   domain_of=None, n_bins: int = 10, sources: bool = True,
+                   device_match: Optional[bool] = None) -> "WalkScore":
+        """How good were the forecasts of a back-test?  ``results`` is the dict ``walk_forward``
+        returns (market id -> consensus dict, in walk order); every market is scored against the
+        store's own outcome (a RESOLVED market with an outcome; any other counts as unresolved):
+        Brier score, log loss, accuracy (the ``>= 0.5`` vote, market.py:298-301), expected
+        calibration error and the calibration rows, all summed on the GPU in one launch
+        (``batch.score``, reproducible to the bit).  Returns a :class:`WalkScore`:
+
+        ``overall``  the whole history;
+        ``groups``   one :class:`BacktestScore` per pattern list (the markets of ``results`` that
+                     match, per pattern in store order, duplicates kept as ``aggregate_many`` keeps
+                     them; ``device_match`` as there: the member lists come from the glob kernels);
+        ``domains``  with ``domain_of`` (a callable or "category"), one per domain, first seen first;
+        ``sources``  with ``sources=True``, a :class:`SourceScore` per sourceId, interned in
+                     first-seen order as ``summarize_sources`` does, every signal counted;
+                     ``skill`` is the source's Brier score minus the consensus's on the markets it
+                     forecast (markets without a consensus are left out of a source's scores)."""
+        if not isinstance(results, dict):
+            raise TypeError(f"results must be the dict walk_forward returns (got {type(results).__name__})")
+        B = int(n_bins)
+        if not 1 <= B <= batch.SCORE_MAX_BINS:
+            raise ValueError(f"n_bins must be in [1, {batch.SCORE_MAX_BINS}] (got {n_bins})")
+        if domain_of is not None:
+            domain_of = _domain_fn(domain_of)
+        if pattern_lists is not None and any(isinstance(p, str) for p in pattern_lists):
+            raise TypeError("pattern_lists must be a list of pattern lists")
+        pattern_lists = [list(p) for p in pattern_lists] if pattern_lists else []
+        position = {key: i for i, key in enumerate(self._store._markets)}
+        missing = [key for key in results if key not in position]
+        if missing:
+            raise KeyError(f"results names markets the store does not hold: {missing[:3]}")
+        walk = [self._store._markets[key] for key in results]
+        spos = np.array([position[key] for key in results], np.int64)
+        Ms, Mw = len(position), len(walk)
+        empty = BacktestScore.empty(B)
+        if not walk:
+            return WalkScore(empty, [empty for _ in pattern_lists], {}, {})
+        code = np.array([(1 if m.outcome else 0) if m.status == MarketStatus.RESOLVED and m.outcome is not None
+                         else -1 for m in walk], np.int8)
+        cons_w = np.array([float(r["consensus"]) if r.get("consensus") is not None else 0.0
+                           for r in results.values()], np.float64)
+        valid_w = np.array([r.get("consensus") is not None for r in results.values()], np.uint8)
+        # market groups index the arrays by store position (the glob kernels emit those)
+        outcome = np.full(Ms, -1, np.int8)
+        cons = np.zeros(Ms, np.float64)
+        valid = np.zeros(Ms, np.uint8)
+        outcome[spos], cons[spos], valid[spos] = code, cons_w, valid_w
+        lists: List[np.ndarray] = [spos]
+        dnames: List[str] = []
+        if domain_of is not None:
+            by_domain: Dict[str, List[int]] = {}
+            for m, p in zip(walk, spos):
+                d = domain_of(m)
+                if d:
+                    by_domain.setdefault(d, []).append(int(p))
+            dnames = list(by_domain)
+            lists += [np.array(by_domain[d], np.int64) for d in dnames]
+        n_patterns = sum(len(p) for p in pattern_lists)
+        N.require_gpu()
+        dev = N.device()
+        T = batch.to_device(dev)
+        on_device = bool(n_patterns) and self._device_route(n_patterns, device_match)
+        if not on_device:
+            for patterns in pattern_lists:
+                lists.append(np.array([position[str(m.id)] for pattern in patterns
+                                       for m in self._store.list_markets(pattern=pattern)
+                                       if str(m.id) in results], np.int64))
+        goff = np.zeros(len(lists) + 1, np.int64)
+        goff[1:] = np.cumsum([len(x) for x in lists])
+        goff_t, members = T(goff), T(np.concatenate(lists))
+        if on_device:
+            globs, bits = self._store.match_many([p for patterns in pattern_lists for p in patterns])
+            slot_groups = np.zeros(len(pattern_lists) + 1, np.int64)
+            slot_groups[1:] = np.cumsum([len(patterns) for patterns in pattern_lists])
+            rows = torch.tensor(globs.index, dtype=torch.int64, device=dev)
+            pgoff, pmem = batch.glob_members(bits, Ms, rows, slot_groups)
+            inres = torch.zeros(Ms, dtype=torch.bool, device=dev)
+            inres[T(spos)] = True
+            keep = inres[pmem]  # only the markets of the back-test
+            run = torch.zeros(pmem.numel() + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(keep, 0, out=run[1:])
+            goff_t = torch.cat([goff_t, goff_t[-1] + run[pgoff[1:]]])
+            members = torch.cat([members, pmem[keep]])
+        plan = batch.ScorePlan.groups(goff_t, members)
+        ms = batch.score(plan, T(cons), T(outcome), valid=T(valid), n_bins=B)
+        rows_ = BacktestScore.from_result(ms)
+        nd = len(dnames)
+        out = WalkScore(rows_[0], rows_[1 + nd:], dict(zip(dnames, rows_[1:1 + nd])), {})
+        if sources:
+            order = _FirstSeen()
+            off, sid, prob = signals_csr([m.signals for m in walk], order, settlement=True)
+            names = list(order)
+            splan = batch.ScorePlan.by_source(T(off), T(sid), len(names))
+            ss = batch.score_sources(splan, T(prob), T(code), consensus=T(cons_w), valid=T(valid_w), n_bins=B)
+            n, brier, ll, acc, skill = (x.cpu().numpy() for x in (ss.n_scored, ss.brier, ss.log_loss, ss.accuracy,
+                                                                   ss.skill))
+            out.sources = {name: SourceScore(name, int(n[i]), float(brier[i]), float(ll[i]), float(acc[i]),
+                                             float(skill[i])) for i, name in enumerate(names)}
+        N.check_faults(dev, "score_walk")
+        return out
+
+    def sweep_decay(self, store, half_life_days, min_rel, patterns: Optional[List[str]] = None,
+                    domain: Optional[str] = None, n_bins: int = 10,
+                    device_match: Optional[bool] = None) -> List["BacktestScore"]:
+        """The back-test of ``walk_forward(store, patterns, domain, dry_run=True)`` for every point
+        of a grid of decay parameters: one whole-history :class:`BacktestScore` per
+        ``(half_life_days[i], min_rel[j])``, row-major (``params`` names the point).  The
+        settlement trace does not depend on the decay parameters, so it runs once
+        (``store.sweep_decay``, ``batch.walk_sweep``); nothing is written to the store.  The
+        single-scope walk only: a history that spans domains (``walk_forward(domain_of=)``) is
+        not swept here."""
+        if not isinstance(store, NamespacedReliabilityStore):
+            raise TypeError(f"sweep_decay needs a NamespacedReliabilityStore (got {type(store).__name__})")
+        try:
+            hl, mr = [float(x) for x in half_life_days], [float(x) for x in min_rel]
+        except TypeError:
+            raise TypeError("half_life_days and min_rel must be sequences of numbers") from None
+        if not hl or not mr:
+            raise ValueError("sweep_decay needs at least one half_life_days and one min_rel")
+        if any(not h > 0 for h in hl):
+            raise ValueError(f"half_life_days must be > 0 (got {hl})")
+        if any(not 0.0 <= m <= 1.0 for m in mr):
+            raise ValueError(f"min_rel must be in [0, 1] (got {mr})")
+        B = int(n_bins)
+        if not 1 <= B <= batch.SCORE_MAX_BINS:
+            raise ValueError(f"n_bins must be in [1, {batch.SCORE_MAX_BINS}] (got {n_bins})")
+        _, batch_markets, stamps = self._walk_history(patterns, device_match)
+        params = [{"half_life_days": h, "min_rel": m} for h in hl for m in mr]
+        scores = store.sweep_decay(batch_markets, stamps, hl, mr, domain=domain, n_bins=B)
+        if scores is None:
+            return [BacktestScore.empty(B, p) for p in params]
+        flat = batch.ScoreResult(*(getattr(scores, k)[:, 0] for k in ("counts", "sums", "bin_n", "bin_pos", "bin_psum")))
+        rows = BacktestScore.from_result(flat)
+        for r, p in zip(rows, params):
+            r.params = p
+        return rows
 
     def summarize_category(self, category: str) -> Dict[str, Any]:
         markets = self._store.list_markets(pattern=f"{category}:*")

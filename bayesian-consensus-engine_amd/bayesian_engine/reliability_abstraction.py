@@ -420,6 +420,38 @@ class NamespacedReliabilityStore:
         return results, SettleSummary(records, {}, {names[i]: int(total[i]) for i in touched},
                                       {names[i]: int(correct[i]) for i in touched})
 
+    def sweep_decay(self, markets: Sequence[tuple], times: Sequence, half_life_days: Sequence[float],
+                    min_rel: Sequence[float], domain: Optional[str] = None, n_bins: int = 10):
+        """:meth:`walk_forward` as a dry run for every point of a grid of decay parameters, each
+        scored against the batch's outcomes (:func:`batch.walk_sweep`: the settlement trace does
+        not depend on the decay parameters and runs once).  Nothing is written.  Returns the
+        :class:`batch.ScoreResult` of the whole history with a leading grid dimension
+        ``[len(half_life_days) * len(min_rel), 1, ...]`` (``min_rel`` fastest), or None for a
+        history without signals."""
+        markets = [(list(signals), outcome) for signals, outcome in markets]
+        times = list(times)
+        if len(times) != len(markets):
+            raise ValueError(f"times has {len(times)} entries for {len(markets)} markets")
+        t_us = np.array([iso_to_us(t) if isinstance(t, str) else dt_to_us(t) for t in times], np.int64)
+        if (t_us == NO_TIMESTAMP).any():
+            raise ValueError("a market time is empty or unparseable")
+        _, _, target = self._update_scope(domain)
+        rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
+        names = list(rank)
+        if not names:
+            return None
+        offsets, sid, prob = signals_csr([signals for signals, _ in markets], rank)
+        N.require_gpu()
+        dev = N.device()
+        T = batch.to_device(dev)
+        off, prob = T(offsets), T(prob)
+        plan = batch.WalkPlan.build(off, T(sid), prob, T(_outcome_codes(markets)), len(names))
+        table = self._store.load_table(target, names, device=dev)
+        scores, _ = batch.walk_sweep(plan, table, T(t_us), offsets=off, prob=prob, half_life_days=half_life_days,
+                                     min_rel=min_rel, n_bins=n_bins)
+        N.check_faults(dev, "sweep_decay")
+        return scores
+
     def walk_forward_namespaced(self, markets: Sequence[tuple], times: Sequence, domains=None,
                                 market_ids: Optional[Sequence[str]] = None, update_global: bool = False,
                                 dry_run: bool = False):

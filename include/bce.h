@@ -647,6 +647,65 @@ int bce_glob_count(const uint64_t* bits, int64_t M, int64_t P, const int64_t* ro
 int bce_glob_fill(const uint64_t* bits, int64_t M, int64_t P, const int64_t* rows, int64_t R,
                   const int64_t* slot_off, int64_t n_members, int64_t* members, void* stream);
 
+/* ---- scoring a back-test: Brier score, log loss, hits and calibration per group of items -------
+ * The yardstick behind the walk-forward entry points: how good were the forecasts of a history
+ * whose markets have resolved?  A group is a CSR list of items, group g = items
+ * [group_offsets[g], group_offsets[g + 1]) (the layout of bce_aggregate_groups / bce_glob_fill).
+ * Item i reads its forecast v = value[pidx[i]] (n_values entries) and its market m = oidx[i]
+ * (oidx NULL: m = pidx[i]) with o = outcome[m] (int8: -1 unresolved, 0, 1), valid[m] (u8,
+ * nullable: the market's consensus is not None) and base[m] (fp64, nullable: a second forecast of
+ * the same market), all over n_markets.  Two uses:
+ *   market groups  value = consensus, pidx = oidx = members (market indices; groups may overlap,
+ *                  a market may appear twice) -- what bce_glob_fill emits;
+ *   per source     value = prob (per signal), pidx = the signal indices stably sorted by source,
+ *                  oidx = the market of each of them, one group per source, every signal counted
+ *                  (summarize_sources, market.py:279-304); base = consensus.
+ * Item rule, the first that applies: o < 0 -> n_unresolved; valid[m] == 0 -> n_null; not
+ * 0 <= v <= 1 (NaN included), or base given and not 0 <= base[m] <= 1 -> n_bad; else n_scored.
+ * Per scored item: brier += (v - o)^2 (difference, then product, then the add: no contraction);
+ * n_hit += (v >= 0.5) == (o == 1) (market.py:298-301); logloss += -log(max(q, eps)) with
+ * q = o ? v : 1 - v; brier_base += (base[m] - o)^2 when base is given (else 0); calibration bin
+ * b = min((int)(v * n_bins), n_bins - 1): bin_n[b] += 1, bin_pos[b] += (o == 1), bin_psum[b] += v.
+ * Outputs per group (all nullable except counts): counts int64[G][5] = {n_scored, n_hit,
+ * n_unresolved, n_null, n_bad}, sums fp64[G][3] = {brier, logloss, brier_base}, bin_n / bin_pos
+ * int64[G][n_bins], bin_psum fp64[G][n_bins].  An empty group writes zeros.
+ *
+ * REDUCTION SHAPE (every fp64 output depends on the arguments alone -- not on the grid, the CU
+ * count, timing or the other groups of the call; no floating-point atomics):
+ *   1. a group of n items is cut into ceil(n / BCE_SCORE_SEG) segments of BCE_SCORE_SEG
+ *      consecutive items (the last one shorter; an empty group has one empty segment);
+ *   2. inside a segment, lane l of BCE_SCORE_LANES = 256 adds the terms of the segment's items
+ *      l, l + 256, l + 512, ... left to right starting from 0.0; an item that is not scored
+ *      contributes the term 0.0 (x + 0.0 == x for these non-negative terms);
+ *   3. the 256 lane sums p[] are folded by the halving tree: for o = 128, 64, ..., 1:
+ *      p[l] = p[l] + p[l + o] for l < o; the segment's sum is p[0];
+ *   4. the group's sum is 0.0 + segment 0 + segment 1 + ..., left to right.
+ * bin_psum[b] is the same shape over the masked terms (bin == b ? v : 0.0).  One workgroup runs
+ * one segment, so a group of millions of items spreads over the device.
+ *
+ * seg_start int64[G + 1]: seg_start[g + 1] - seg_start[g] = max(1, ceil(n_g / BCE_SCORE_SEG)),
+ * seg_start[0] = 0, n_segments = seg_start[G] (the caller's cumulative sum; batch.ScorePlan);
+ * seg_group int64[n_segments]: the group of every segment (seg_start[g] <= s < seg_start[g + 1]).
+ * scratch: device buffer of bce_score_scratch_bytes(n_segments, n_bins) bytes, 8-byte aligned
+ * (one row of partial results per segment).  Nothing synchronises.
+ * Bad arguments (a negative size, n_bins outside [1, BCE_SCORE_MAX_BINS], eps < 0 or NaN, a NULL
+ * required pointer) return BCE_EINVAL before anything touches the GPU.  On the device, group
+ * offsets that decrease or leave [0, n_items] (the group reads as empty), a segment table that
+ * does not hold every group's own segment count (the group's outputs are zeros), a seg_group
+ * entry that is not the segment's group (the segment scores nothing) and a pidx /
+ * oidx outside its array (the item counts as n_bad) raise the device fault word
+ * (bce_fault_check); nothing is read or written outside the arrays. */
+#define BCE_SCORE_MAX_BINS 32
+#define BCE_SCORE_SEG 2048  /* items of a segment */
+#define BCE_SCORE_LANES 256 /* lane partials of a segment */
+int64_t bce_score_scratch_bytes(int64_t n_segments, int32_t n_bins);
+int bce_score_groups(const int64_t* group_offsets, int64_t n_groups, const int64_t* seg_start,
+                     const int64_t* seg_group, int64_t n_segments, const int64_t* pidx, const int64_t* oidx, int64_t n_items,
+                     const double* value, int64_t n_values, const int8_t* outcome, const uint8_t* valid,
+                     const double* base, int64_t n_markets, int32_t n_bins, double eps, void* scratch,
+                     int64_t scratch_bytes, int64_t* counts, double* sums, int64_t* bin_n,
+                     int64_t* bin_pos, double* bin_psum, void* stream);
+
 /* ---- JSONL front end (host C++, no GPU): SURVEY §8 f2 -----------------------------------
  *
  * Replaces, for a batch: cli._cmd_consensus_legacy / _cmd_consensus (cli.py:25-52,163-174)
