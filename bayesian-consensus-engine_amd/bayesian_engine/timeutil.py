@@ -3,9 +3,11 @@
 The reference stores ``updated_at`` as ISO text and parses it on every read
 (``decay.py:140-145``, ``reliability.py:115-116``).  The engine parses once at bulk
 load and keeps int64 microseconds in HBM; elapsed days are then
-``(double)(now_us - t_us) / 1e6 / 86400.0`` on the GPU, which equals
-``timedelta.total_seconds() / 86400.0`` bit for bit (int-microseconds / 10**6 is
-correctly rounded in both).
+``total_seconds(now_us - t_us) / 86400.0`` on the GPU (``csrc/decay_device.hpp``).
+``timedelta.total_seconds()`` is CPython's ``int_us / 10**6``, rounded once.
+``(double)n / 1e6`` is the same double only while ``n < 2**53`` (285 years), where the
+conversion is exact; for wider spans, up to year 1 against year 9999, the kernel rounds
+the quotient once from integers, so both agree bit for bit over every pair of datetimes.
 """
 from __future__ import annotations
 

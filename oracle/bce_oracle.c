@@ -118,10 +118,25 @@ double orc_apply_decay(double r, double elapsed_days, double half_life_days, dou
     return py_max(min_rel, py_min(1.0, decayed));
 }
 
-/* decay.py:140-145: timedelta.total_seconds() == int_us / 10**6 correctly rounded. */
+/* timedelta.total_seconds() is CPython's int_us / 10**6: one rounding.  Below 2^53 us (285
+ * years) the conversion to double is exact and the division is that rounding (a negative
+ * difference ends as 0.0 days however it rounds).  From 2^53 on the conversion would round
+ * too, so the quotient is rounded once from integers: 10^6 = 2^6 * 15625, n = a * 15625 + b,
+ * exponent e of floor(n / 10^6) = a >> 6, significand (a << s) + (b << s) / 15625 to nearest
+ * with s = 46 - e (3..13); 15625 is odd, so there are no ties. */
+static double total_seconds(int64_t n) {
+    if (n < ((int64_t)1 << 53)) return (double)n / 1e6;
+    const uint64_t a = (uint64_t)n / 15625u, b = (uint64_t)n % 15625u;
+    const int s = 46 - (63 - __builtin_clzll(a >> 6));
+    const uint64_t bs = b << s, rem = bs % 15625u;
+    const uint64_t m = (a << s) + bs / 15625u + (2 * rem > 15625u);
+    return ldexp((double)m, -(s + 6));
+}
+
+/* decay.py:140-145 */
 double orc_days_since(int64_t now_us, int64_t t_us) {
     if (t_us == ORC_NO_TIMESTAMP) return 0.0;
-    const double secs = (double)(now_us - t_us) / 1e6;
+    const double secs = total_seconds(now_us - t_us);
     return py_max(0.0, secs / 86400.0);
 }
 

@@ -203,6 +203,8 @@ def test_glibc_pow2_restatement_matches_libm(tmp_path):
     # pow(2.0, y) of the decay factor (decay.py:58) too: bit-exact where exp2 is not
     assert f["pow2_tested"] > 3_900_000 and f["pow2_mismatches"] == 0
     assert f["exp2_differs"] > 100
+    # the ratio list of tests/golden/decay_edges.json, exponents formed as the kernels form them
+    assert f["edge_tested"] >= 200 and f["edge_mismatches"] == 0
 
 
 def _py_round_host(x, nd):

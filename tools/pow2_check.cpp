@@ -1,6 +1,7 @@
 // pow2_check.cpp -- host check of csrc/glibc_pow.hpp against the system libm (test tooling).
 //   g++ -O2 -ffp-contract=off -DBCE_POW_HOST_TEST -I<csrc> tools/pow2_check.cpp -o pow2_check -lm
-//   ./pow2_check N      -> "tested=T mismatches=K d_mul_differs=D pow2_tested=.. pow2_mismatches=.. exp2_differs=.."
+//   ./pow2_check N      -> "tested=T mismatches=K d_mul_differs=D pow2_tested=.. pow2_mismatches=.. exp2_differs=..
+//                           edge_tested=.. edge_mismatches=.."
 // Inputs per round: a difference of two U[0,1) (the tie-break's c - mean), an odd 27-28-bit
 // significand scaled down (exact-midpoint squares), an arbitrary positive bit pattern
 // (subnormal .. huge) and a negative tiny value (underflowing squares).
@@ -62,7 +63,39 @@ int main(int argc, char** argv) {
       if (bits(a) != bits(exp2(y))) ++ex2;
     }
   }
-  printf("tested=%ld mismatches=%ld d_mul_differs=%ld pow2_tested=%ld pow2_mismatches=%ld exp2_differs=%ld\n", tot, bad,
-         dmul, tot2, bad2, ex2);
-  return (bad | bad2) != 0;
+  // the elapsed/half-life ratios of tests/golden/decay_edges.json (gen_decay_edges.py ratios()):
+  // the 1 + y path, exp table boundaries, the special-case threshold, subnormal and vanishing
+  // factors -- as the kernels form the exponent, -(q * h) / h.  A fault here is a fault of the
+  // restatement itself; one that only tests/test_gpu_decay_edges.py sees is the device compile's.
+  long tot3 = 0, bad3 = 0;
+  {
+    double q[64];
+    int nq = 0;
+    const double head[] = {5e-324, 1e-300, 0x1p-66, 0x1p-65, 0x1p-64, 0x1p-54, 0x1p-53, 1.0, 2.0, 3.0};
+    for (double v : head) q[nq++] = v;
+    const int ks[] = {1, 63, 128, 129, 5000};
+    for (int k : ks) {
+      const double x = k / 128.0;
+      q[nq++] = nextafter(x, 0.0); q[nq++] = x; q[nq++] = nextafter(x, INFINITY);
+    }
+    const double tail[] = {738.0, 738.6, 738.7, 739.0, 1021.9999, 1022.0, 1022.5, 1050.3, 1073.0, 1074.0,
+                           1074.5, 1075.0, 1076.0, 1e4, 1e300, INFINITY};
+    for (double v : tail) q[nq++] = v;
+    const double hs[] = {1e-3, 1.0, 30.0, 1e5, 1e300, INFINITY};
+    for (int i = 0; i < nq; ++i)
+      for (double h : hs) {
+        volatile double e = q[i] * h;
+        const double y = -e / h;
+        if (isnan(y)) continue;  // inf / inf: CPython answers NaN itself
+        ++tot3;
+        const double a = pow(2.0, y), b = bce_pow::pow_base2(y);
+        if (bits(a) != bits(b)) {
+          if (bad3 < 5) printf("edge y=%a libm=%a restated=%a\n", y, a, b);
+          ++bad3;
+        }
+      }
+  }
+  printf("tested=%ld mismatches=%ld d_mul_differs=%ld pow2_tested=%ld pow2_mismatches=%ld exp2_differs=%ld "
+         "edge_tested=%ld edge_mismatches=%ld\n", tot, bad, dmul, tot2, bad2, ex2, tot3, bad3);
+  return (bad | bad2 | bad3) != 0;
 }
