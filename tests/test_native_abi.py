@@ -28,6 +28,83 @@ def test_library_exports_every_declared_symbol():
     assert set(declared) == set(N.EXPORTED), "ctypes signature table out of sync with bce.h"
 
 
+def _header(strip_defines: bool):
+    src = open(os.path.join(ROOT, "include", "bce.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    if strip_defines:
+        src = "\n".join(line for line in src.split("\n") if not line.lstrip().startswith("#"))
+    return src
+
+
+def _c_kind(ctype: str, is_return: bool = False) -> str:
+    """A C type of the header as the kind of ctypes type that must stand for it."""
+    t = " ".join(ctype.replace("*", " * ").split())
+    if is_return and t == "const char *":
+        return "char_p"
+    if "*" in t:
+        return "ptr"
+    kinds = {"int64_t": "i64", "int32_t": "i32", "int": "i32", "double": "f64"}
+    if is_return and t == "void":
+        return "void"
+    assert t in kinds, f"the header uses a type this test does not know: {ctype!r}"
+    return kinds[t]
+
+
+def _ctypes_kind(t) -> str:
+    kinds = {C.c_void_p: "ptr", C.c_int64: "i64", C.c_int32: "i32", C.c_int: "i32", C.c_double: "f64",
+             C.c_char_p: "char_p", None: "void"}
+    assert t in kinds, f"_SIGS uses a ctypes type this test does not know: {t!r}"
+    return kinds[t]
+
+
+def _prototypes():
+    """``{name: (return kind, [argument kinds])}`` of every ``bce_*`` prototype of the header."""
+    out = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][A-Za-z0-9_ ]*?[\s\*]+)\b(bce_[a-z0-9_]+)\s*\(([^)]*)\)\s*;",
+                                      _header(strip_defines=True)):
+        args = [" ".join(a.split()) for a in args.split(",")]
+        if args == ["void"] or args == [""]:
+            args = []
+        kinds = []
+        for a in args:
+            m = re.fullmatch(r"(.*?[\s\*])([A-Za-z_][A-Za-z0-9_]*)", a)  # type, then the parameter's name
+            assert m, f"{name}: cannot split the parameter {a!r}"
+            kinds.append("ptr" if m.group(2) == "stream" else _c_kind(m.group(1)))
+        assert name not in out, f"{name} is declared twice"
+        out[name] = (_c_kind(ret, is_return=True), kinds)
+    return out
+
+
+def test_ctypes_signatures_match_the_header_types():
+    protos = _prototypes()
+    assert len(protos) >= 57, f"only {len(protos)} prototypes parsed from include/bce.h"
+    assert set(protos) == set(N._SIGS)
+    assert C.sizeof(C.c_int) == 4
+    for name, (ret, args) in protos.items():
+        res, argtypes = N._SIGS[name]
+        assert _ctypes_kind(res) == ret, f"{name}: return type {res!r}, the header says {ret}"
+        assert len(argtypes) == len(args), f"{name}: {len(argtypes)} arguments, the header has {len(args)}"
+        for i, (have, want) in enumerate(zip(argtypes, args)):
+            assert _ctypes_kind(have) == want, f"{name}: argument {i} is {have!r}, the header says {want}"
+
+
+def test_constants_match_the_header():
+    from bayesian_engine import batch
+    src = _header(strip_defines=False)
+    define = {k: v for k, v in re.findall(r"^#define[ \t]+(BCE_[A-Z0-9_]+)[ \t]+(\S+)[ \t]*$", src, flags=re.M)}
+    enum = {k: int(v) for k, v in re.findall(r"\b(BCE_[A-Z0-9_]+)\s*=\s*(-?\d+)", src)}
+    assert int(define["BCE_NBINS"]) == N.NBINS
+    assert (enum["BCE_PAIR_STORE"], enum["BCE_PAIR_NAMESPACED"], enum["BCE_PAIR_RAW"]) == \
+        (N.PAIR_STORE, N.PAIR_NAMESPACED, N.PAIR_RAW)
+    assert batch._PAIR_MODES == {"store": N.PAIR_STORE, "namespaced": N.PAIR_NAMESPACED, "raw": N.PAIR_RAW}
+    for name in ("SCORE_MAX_BINS", "SCORE_SEG", "SCORE_LANES"):
+        assert int(define["BCE_" + name]) == getattr(N, name) == getattr(batch, name), name
+    for name in ("GLOB_MAX_OPS", "GLOB_MAX_RANGES"):
+        assert int(define["BCE_" + name]) == getattr(batch, name), name
+    assert define["BCE_NO_TIMESTAMP"] == "INT64_MIN" and N.NO_TIMESTAMP == -(2 ** 63)
+    assert (enum["BCE_MODE_EXACT"], enum["BCE_MODE_FAST"]) == (N.MODE_EXACT, N.MODE_FAST)
+
+
 def test_abi_version_and_device_count():
     lib = N.load_library()
     assert lib.bce_abi_version() == 3
