@@ -26,7 +26,7 @@ class TieBreakResult:
 class TiePlan:
     """Markets of <= 32 agents bucketed by length for the lane-per-market tie-break: lists of the
     markets with <= 8, 9..16 and 17..32 agents, each run by a kernel walking 8 / 16 / 32
-    positions per lane over rows gathered into LDS (tiebreak.hip GATHER) -- or None when
+    positions per lane over rows gathered into LDS (tiebreak_lpm.hip GATHER) -- or None when
     bucketing would not pay (a uniform batch: contiguous tiles, the FULL-tile kernel)."""
 
     buckets: Optional[list]  # [(device int32 list, max_len)], or None: contiguous tiles

@@ -68,6 +68,24 @@ __device__ __forceinline__ int push_i32(int v, int dst_lane) {
   return __builtin_amdgcn_ds_permute(dst_lane << 2, v);
 }
 
+// Lane l's 64-bit value as a wave-uniform one: a v_readlane (v_readfirstlane: the first
+// active lane's) per half.
+__device__ __forceinline__ double readlane_f64(double v, int l) {
+  const int2 x = *reinterpret_cast<const int2*>(&v);
+  int2 y;
+  y.x = __builtin_amdgcn_readlane(x.x, l);
+  y.y = __builtin_amdgcn_readlane(x.y, l);
+  return *reinterpret_cast<const double*>(&y);
+}
+__device__ __forceinline__ int64_t readlane_i64(int64_t v, int l) {
+  return ((int64_t)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) |
+         (uint32_t)__builtin_amdgcn_readlane((int)v, l);
+}
+__device__ __forceinline__ int64_t readfirstlane_i64(int64_t v) {
+  return ((int64_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+         (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
 // Bitonic sort (ascending) of one 32-bit key per lane inside aligned G-lane segments.
 template <int G>
 __device__ __forceinline__ unsigned bitonic_sort_seg(unsigned key, int l) {

@@ -97,7 +97,7 @@ int* split_slot(int ticket, hipStream_t st) {
   if (!c || !c->split) return nullptr;
   static_assert(kQueueSlots == 64, "split_last size");
   // tickets make reuse safe, on any stream: PART 1 raises a word to its ticket (atomicMax) and
-  // PART 2 runs whenever the word holds its own or a newer pair's ticket (tiebreak.hip)
+  // PART 2 runs whenever the word holds its own or a newer pair's ticket (tiebreak_lpm.hip)
   const unsigned k = c->split_next.fetch_add(1) % kQueueSlots;
   int* w = c->split + (size_t)k * kSplitWords;
   // After the 30-bit ticket counter wraps, the slot's words still hold the old, larger tickets

@@ -356,8 +356,7 @@ __global__ __launch_bounds__(64) void consensus_lpm_kernel(ConsArgs a) {
     for (int q = 0; q < kWave; ++q) {
       const int nq = __builtin_amdgcn_readlane(n, q);
       if (nq == 0) continue;
-      const int64_t oq = ((int64_t)__builtin_amdgcn_readlane((int)(off >> 32), q) << 32) |
-                         (uint32_t)__builtin_amdgcn_readlane((int)off, q);
+      const int64_t oq = readlane_i64(off, q);
       if (lane < nq) dma4(a.sid + oq + lane, sS + q * SST);
       if (lane < 2 * nq) dma4(reinterpret_cast<const uint32_t*>(a.prob + oq) + lane, sP + q * PST);
       if (2 * nq > kWave && lane < 2 * nq - kWave)
@@ -858,10 +857,6 @@ void consensus_pipe_kernel(ConsArgs a) {
         tbE = a.offsets[(m0 + TM < M) ? m0 + TM : M];
       }
     };
-    auto rl = [&](int64_t v, int i) -> int64_t {
-      return ((int64_t)__builtin_amdgcn_readlane((int)(v >> 32), i) << 32) |
-             (uint32_t)__builtin_amdgcn_readlane((int)v, i);
-    };
     // validation (core.py:59-60) for the compute waves: the tail of the arrays that no
     // 16-B chunk covers is loaded here, then every position's range check becomes one bit
     // of sBad (ballot per 64 positions, contiguous conflict-free reads); NaN passes
@@ -935,7 +930,7 @@ void consensus_pipe_kernel(ConsArgs a) {
         }
       }
       const int64_t t = (int64_t)blockIdx.x + i * gridDim.x;
-      const int64_t B = rl(tbB, (int)(k & 63)), E = rl(tbE, (int)(k & 63));
+      const int64_t B = readlane_i64(tbB, (int)(k & 63)), E = readlane_i64(tbE, (int)(k & 63));
       const int64_t m0 = t * TM, m1 = (m0 + TM < M) ? m0 + TM : M;
       const int64_t Bs = B & ~3ll, Bp = B & ~1ll;
       const int64_t es = (E < Nf4) ? ((E + 3) & ~3ll) : Nf4;
@@ -1019,8 +1014,7 @@ void consensus_pipe_kernel(ConsArgs a) {
       }
     }
     const int64_t tile0 = sTile[s];
-    const int64_t tile = ((int64_t)__builtin_amdgcn_readfirstlane((int)(tile0 >> 32)) << 32) |
-                         (uint32_t)__builtin_amdgcn_readfirstlane((int)tile0);  // uniform
+    const int64_t tile = readfirstlane_i64(tile0);  // uniform
     if (tile < 0) {
       __hip_atomic_store(&sFree[s], seq + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
       break;

@@ -202,7 +202,7 @@ int launch_wide_len(int64_t max_len, const ConsArgs& a, hipStream_t st);
 // Resident workgroups (every CU's share) of the wide kernel launch_wide_len would pick.
 int64_t wide_resident(int64_t max_len, int32_t mode, int32_t n_sources);
 // kSplitWords words (one per wave of the grid) for a tie-break FULL/rest launch pair
-// (tiebreak.hip; written with a per-launch ticket)
+// (tiebreak_lpm.hip; written with a per-launch ticket)
 constexpr int kSplitWords = 4096;
 int* split_slot(int ticket, hipStream_t st);  // clears the slot on `st` when the ticket counter wrapped
 

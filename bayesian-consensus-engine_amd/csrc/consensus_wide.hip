@@ -423,11 +423,6 @@ __device__ __forceinline__ double dpp_f64(double v) {
                                           false);
   return __hiloint2double(hi, lo);
 }
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane((int)(uint32_t)__double_as_longlong(v), l);
-  const int hi = __builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)__double_as_longlong(v) >> 32), l);
-  return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ double wave_sum_fixed(double v) {
   v = v + dpp_f64<0x128>(v);  // row_ror:8
   v = v + dpp_f64<0x124>(v);  // row_ror:4

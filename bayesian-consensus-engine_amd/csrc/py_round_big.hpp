@@ -16,7 +16,7 @@
 // Big integers are 28 little-endian 32-bit limbs (896 bits >= m * 5^323, 804 bits), so the
 // same code runs on the host and the device.  This is the rare path (predictions below
 // ~1e-7 at ndigits >= 23, any prediction >= 4e15 at ndigits <= -16): the tie-break kernels
-// are instantiated separately for it (tiebreak.hip), keeping the ndigits = 6 path unchanged.
+// are instantiated separately for it (tiebreak.hip, tiebreak_lpm.hip), keeping the ndigits = 6 path unchanged.
 #pragma once
 #include <math.h>
 #include <stdint.h>

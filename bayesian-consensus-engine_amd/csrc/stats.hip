@@ -154,13 +154,6 @@ constexpr int kVoteRows = 16;
 // readlane pair per row into SGPRs -- instead of kVoteRows scalar loads held across the batch
 // (32 SGPRs, which spilled to VGPR lanes: ~7 writelane / readlane per row).
 constexpr bool kVoteWLane = true;
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const int2 x = *reinterpret_cast<const int2*>(&v);
-  int2 y;
-  y.x = __builtin_amdgcn_readlane(x.x, l);
-  y.y = __builtin_amdgcn_readlane(x.y, l);
-  return *reinterpret_cast<const double*>(&y);
-}
 // v_writelane_b32 (the LLVM intrinsic; clang has no builtin for it): lane l of the result =
 // src (wave-uniform), every other lane keeps old -- a row's vote ballot into its agent's lane
 // without a (lane == q) mask per row held in SGPRs

@@ -996,7 +996,7 @@ def test_tiebreak_ragged_lane_kernel_vs_oracle(precision):
 def test_tiebreak_length_buckets_vs_oracle(precision):
     """batch.tiebreak_plan: a ragged batch of 0..32-agent markets bucketed by length (<= 8,
     9..16, 17..32) and run by the gather-staged kernels walking 8 / 16 / 32 positions per lane
-    (tiebreak.hip GATHER), the bucket edges 8 / 9 / 16 / 17 / 32 and empty / single-agent
+    (tiebreak_lpm.hip GATHER), the bucket edges 8 / 9 / 16 / 17 / 32 and empty / single-agent
     markets included: every output bit-exact against the oracle, and identical to the
     contiguous-tile launch (max_len=32) on every defined slot.  Exotic precisions take the
     EXOTIC gather kernels."""

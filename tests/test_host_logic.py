@@ -261,7 +261,7 @@ def test_big_integer_round_matches_cpython(nd):
 
 
 def test_markstein_quotients_match_ieee_division(tmp_path):
-    """The tie-break FULL kernel's divisions without a divide (tiebreak.hip tb_div_small,
+    """The tie-break FULL kernel's divisions without a divide (tiebreak_common.hpp tb_div_small,
     bce_device.hpp py_round_nd_sel): RN(x * RN(1/c)) with one FMA correction equals the IEEE
     quotient -- for k / 10^nd (integer k < 2^53, nd 0..22) and for x / c (c = 1..32, |x| in
     [2^-1000, 2^1000]).  tools/check_markstein.c at 1/100 of its full sample (the full run,

@@ -15,6 +15,7 @@ a replacement whose old text is missing fails the build (the patch went stale).
 import argparse
 import json
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -23,11 +24,18 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bayesian-consensus-engine_amd", "csrc")
 OUT = os.path.join(ROOT, "tools", "bin", "variants")  # gitignored; travels to the GPU box
-# the translation units of csrc/Makefile (SRCS, CPPSRCS)
-SRCS = ["capi.hip", "consensus.hip", "consensus_api.hip", "consensus_tab.hip", "consensus_wide.hip", "plan.hip",
-        "elementwise.hip", "tiebreak.hip", "stats.hip", "aggregate.hip", "reestimate_csr.hip", "settle.hip",
-        "pair_scope.hip", "glob.hip"]
-CPP_SRCS = ["jsonl.cpp", "errors.cpp"]
+
+
+def _makefile_list(name):
+    """The words of `name := ...` in csrc/Makefile, which keeps the only list of translation units."""
+    m = re.search(rf"^{name} := (.*)$", open(os.path.join(CSRC, "Makefile")).read(), re.M)
+    if not m:
+        raise SystemExit(f"csrc/Makefile has no {name}")
+    return m.group(1).split()
+
+
+SRCS = _makefile_list("SRCS")
+CPP_SRCS = _makefile_list("CPPSRCS")
 
 _XPOSE_NEW = """  for (int i = 0; i < N; ++i)
     if (!(i & 4)) bfly_r8(r[i], r[i | 4], lane);

@@ -32,6 +32,8 @@ OUT = tab_variants.OUT
 # tie-break's LDS-DMA staging (kTbStageMode 1/2), pre-issued batches (kTbPreBatch) and next-array
 # touches (kTbTouchNext) were removed from csrc/ (verdict r04 item 7); their A/Bs are recorded in
 # DESIGN.md §4.2 / §4.9 and profiles/archive/r04c, r04e, r04f, r04k, r04m, r04aa.
+# c5nopf (MFMA pass without its next-batch prefetch) became the shipped state (kMfmaPrefetch = false);
+# c5pf turns the prefetch back on.  The tie-break entries follow the lane kernel to tiebreak_lpm.hip.
 VARIANTS = {
     "wbase": [],
     # small planned calls without the bin merges / merging below 3 resident rounds (shipped: 6)
@@ -41,21 +43,21 @@ VARIANTS = {
     # loop; shipped: at the top of the tile, as round 4)
     "tablate": [("consensus_tab.hip", "constexpr bool kTabMetaEarly = true;", "constexpr bool kTabMetaEarly = false;")],
     # tie-break FULL tiles: staging batches of the predictions / confidences (shipped: 8)
-    "tbpc16": [("tiebreak.hip", "constexpr int kTbFullBatchPC = 8;", "constexpr int kTbFullBatchPC = 16;")],
-    "tbpc4": [("tiebreak.hip", "constexpr int kTbFullBatchPC = 8;", "constexpr int kTbFullBatchPC = 4;")],
+    "tbpc16": [("tiebreak_lpm.hip", "constexpr int kTbFullBatchPC = 8;", "constexpr int kTbFullBatchPC = 16;")],
+    "tbpc4": [("tiebreak_lpm.hip", "constexpr int kTbFullBatchPC = 8;", "constexpr int kTbFullBatchPC = 4;")],
     # tie-break staging / flush without the nontemporal hints (0.727-0.730 vs 0.712 ms, r04j)
-    "tbnont": [("tiebreak.hip", "constexpr bool kTbNtLoad = true;", "constexpr bool kTbNtLoad = false;"),
-               ("tiebreak.hip", "constexpr bool kTbNtStore = true;", "constexpr bool kTbNtStore = false;")],
-    "tbnopre": [("tiebreak.hip", "constexpr bool kTbPrefetchMeta = true;", "constexpr bool kTbPrefetchMeta = false;")],
+    "tbnont": [("tiebreak_lpm.hip", "constexpr bool kTbNtLoad = true;", "constexpr bool kTbNtLoad = false;"),
+               ("tiebreak_lpm.hip", "constexpr bool kTbNtStore = true;", "constexpr bool kTbNtStore = false;")],
+    "tbnopre": [("tiebreak_lpm.hip", "constexpr bool kTbPrefetchMeta = true;", "constexpr bool kTbPrefetchMeta = false;")],
     # FULL tiles: staging batches (shipped: 8 and 8)
-    "tbwr4": [("tiebreak.hip", "constexpr int kTbFullBatchWR = 8;", "constexpr int kTbFullBatchWR = 4;")],
-    "tbwr16": [("tiebreak.hip", "constexpr int kTbFullBatchWR = 8;", "constexpr int kTbFullBatchWR = 16;")],
-    "tbpc16wr16": [("tiebreak.hip", "constexpr int kTbFullBatchWR = 8;", "constexpr int kTbFullBatchWR = 16;"),
-                   ("tiebreak.hip", "constexpr int kTbFullBatchPC = 8;", "constexpr int kTbFullBatchPC = 16;")],
-    # C5 MFMA pass: two accumulator chains / no next-batch prefetch (8 waves per SIMD)
-    # (shipped: one chain, 8-row batches, the next batch issued before the chain, 6 waves)
+    "tbwr4": [("tiebreak_lpm.hip", "constexpr int kTbFullBatchWR = 8;", "constexpr int kTbFullBatchWR = 4;")],
+    "tbwr16": [("tiebreak_lpm.hip", "constexpr int kTbFullBatchWR = 8;", "constexpr int kTbFullBatchWR = 16;")],
+    "tbpc16wr16": [("tiebreak_lpm.hip", "constexpr int kTbFullBatchWR = 8;", "constexpr int kTbFullBatchWR = 16;"),
+                   ("tiebreak_lpm.hip", "constexpr int kTbFullBatchPC = 8;", "constexpr int kTbFullBatchPC = 16;")],
+    # C5 MFMA pass: two accumulator chains / the next batch issued before the chain (6 waves per SIMD)
+    # (shipped: one chain, 8-row batches, no next-batch prefetch, 8 waves)
     "c5acc2": [("stats.hip", "constexpr bool kMfmaTwoAcc = false;", "constexpr bool kMfmaTwoAcc = true;")],
-    "c5nopf": [("stats.hip", "constexpr bool kMfmaPrefetch = true;", "constexpr bool kMfmaPrefetch = false;")],
+    "c5pf": [("stats.hip", "constexpr bool kMfmaPrefetch = false;", "constexpr bool kMfmaPrefetch = true;")],
     # EXACT piped chain wave with the 8-term chain_add (shipped: chain_add_deep, 16-term steps)
     "nodeep": [("consensus_wide.hip", "constexpr bool kWideChainDeep = true;", "constexpr bool kWideChainDeep = false;")],
     # EXACT chains on every lane of the chain wave (lane % 3 picks the chain; shipped: lanes 0..2)
@@ -63,9 +65,6 @@ VARIANTS = {
     # C5 exact pass 1 on 256- / 512-thread workgroups (shipped: 1024)
     "c5b256": [("stats.hip", "constexpr int kVoteBlock = 1024;", "constexpr int kVoteBlock = 256;")],
     "c5b512": [("stats.hip", "constexpr int kVoteBlock = 1024;", "constexpr int kVoteBlock = 512;")],
-    # C5 exact pass 1: blocks in launch order over the columns (shipped: one contiguous column
-    # slice per XCD)
-    "c5noxcd": [("stats.hip", "constexpr bool kVoteXcd = true;", "constexpr bool kVoteXcd = false;")],
     # C5 exact and MFMA passes in launch order (shipped: one contiguous column slice per XCD)
     "c5noxcd": [("stats.hip", "constexpr bool kVoteXcd = true;", "constexpr bool kVoteXcd = false;")],
     "wdiv": [("consensus_wide.hip", "constexpr bool kWideFastRecip = true;", "constexpr bool kWideFastRecip = false;")],
@@ -77,10 +76,9 @@ VARIANTS = {
     "aggnoasm": [("aggregate.hip", "constexpr bool kAggChainAsm = true;", "constexpr bool kAggChainAsm = false;")],
     "aggw1": [("aggregate.hip", "constexpr int kAggWpe = 6;", "constexpr int kAggWpe = 1;")],
     "tab4w": [("consensus_tab.hip", "constexpr int kTabWaves = 8;", "constexpr int kTabWaves = 4;")],
-    "tbkvsort": [("tiebreak.hip", "constexpr bool kTbFullKeysInLds = true;", "constexpr bool kTbFullKeysInLds = false;")],
+    "tbkvsort": [("tiebreak_lpm.hip", "constexpr bool kTbFullKeysInLds = true;", "constexpr bool kTbFullKeysInLds = false;")],
     # tie-break without the FULL-tile kernel (one general launch)
-    "tbnofull": [("tiebreak.hip", "bool split = !EXOTIC && a.rmode == 0 && al16(a.pred)",
-                  "const bool split = false && al16(a.pred)")],
+    "tbnofull": [("tiebreak_lpm.hip", "constexpr bool kTbFullKernel = true;", "constexpr bool kTbFullKernel = false;")],
     # ---- ablations (timing only; outputs are wrong by construction -- no parity gate) ----
     # the sort network run twice (the second pass on sorted keys costs the same)
     "xsort2": [("consensus_wide.hip", "  wide_sort<NN, NW, R>(key, sX, t, lane);\n",
