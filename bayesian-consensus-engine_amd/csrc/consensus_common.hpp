@@ -1,7 +1,9 @@
 // consensus_common.hpp -- declarations shared by the consensus translation units
-// (consensus.hip: list / long-market kernels and their launchers; consensus_tab.hip: the
-// LDS-table kernel for contiguous short markets; consensus_wide.hip: 64 < n <= 4096;
-// consensus_api.hip: the C entries that pick among them; plan.hip: the planners).
+// (consensus.hip: the seg and long-market kernels and the choice among the short-market
+// kernels; consensus_lane.hip: the lane-per-market kernels for n <= 32, their shared pieces in
+// consensus_lane.hpp; consensus_tab.hip: the LDS-table kernel for contiguous short markets;
+// consensus_wide.hip: 64 < n <= 4096; consensus_api.hip: the C entries that pick among them;
+// plan.hip: the planners).
 #pragma once
 #pragma clang fp contract(off)
 
@@ -195,6 +197,17 @@ int launch_tab32(const ConsArgs& a, hipStream_t st);
 int launch_seg_for_len(int max_len, const ConsArgs& a, hipStream_t st);
 int launch_long_lds(const ConsArgs& a, hipStream_t st);
 int launch_long_global(ConsArgs a, void* scratch, int64_t stride, hipStream_t st);
+// ... and the persistent launch its short-market kernels and the lane kernels share: a grid of
+// min(units, resident workgroups), `fallback` workgroups per CU if the occupancy query fails.
+int launch_persistent(void (*kernel)(ConsArgs), int threads, int fallback, int64_t units, const char* name,
+                      const ConsArgs& a, hipStream_t st);
+inline int64_t ceil_div(int64_t n, int64_t d) { return (n + d - 1) / d; }
+
+// consensus_lane.hip: the lane-per-market kernels for n <= G in {8, 16, 32}: market lists (lpm),
+// contiguous markets with each wave loading its own tile (flat) or behind a loader wave (pipe,
+// which needs all outputs, n_signals >= 4 and n_sources < 2^25).
+enum class LaneKernel { Lpm, Flat, Pipe };
+int launch_lane(LaneKernel k, int G, const ConsArgs& a, hipStream_t st);
 
 // Register-sort kernel (consensus_wide.hip) for 64 < n <= 4096: keys (sid << ib) | index with
 // ib = log2 of the bin's padded size (7..12), 32 bits while n_sources <= 2^(32 - ib), else 64.
