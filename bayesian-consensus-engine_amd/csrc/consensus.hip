@@ -1,7 +1,8 @@
 // consensus.hip -- batched core.compute_consensus (core.py:63-179) over CSR markets: the seg
 // and long kernels, their launchers, and launch_seg_for_len, which picks the kernel for markets
 // of up to 64 signals (the lane-per-market kernels are consensus_lane.hip, the LDS-table kernel
-// is consensus_tab.hip, the wide one consensus_wide.hip; the C entries are consensus_api.hip).
+// is consensus_tab.hip, the wide one consensus_wide.hip over wide_sort.hpp and ordered_chain.hpp;
+// the C entries are consensus_api.hip).
 //
 // Kernels by market length (launch_seg_for_len / launch_wide_len pick them):
 //  consensus_pipe_kernel<G>    contiguous markets, n <= G in {8,16,32}, all outputs
@@ -453,7 +454,7 @@ __global__ __launch_bounds__(kLongThreads) void consensus_long_kernel(ConsArgs a
       Pr[j] = avg * w;  // core.py:136
       Cv[j] = c * w;    // core.py:142
       const int64_t p = off + j;
-      if (a.usid) a.usid[p] = s | (is_present(a.pbits, s) ? 0 : (int32_t)0x80000000);
+      if (a.usid) a.usid[p] = s | (int32_t)cold_flag(a.pbits[s >> 5], s);
       if (a.weight) a.weight[p] = w;
     }
     __syncthreads();

@@ -2,7 +2,8 @@
 // picked by the longest market), bce_consensus_planned / bce_consensus_planned_device (the
 // launches plan_schedule lists for a length-binned plan, plan_host.hpp), and the two small
 // kernels that go with them, bce_validate_csr and bce_table_pack.  The consensus kernels and
-// their launchers are consensus.hip, consensus_lane.hip, consensus_tab.hip and consensus_wide.hip.
+// their launchers are consensus.hip, consensus_lane.hip, consensus_tab.hip and consensus_wide.hip
+// (with wide_sort.hpp and ordered_chain.hpp).
 #include "consensus_common.hpp"
 #include "plan_host.hpp"
 

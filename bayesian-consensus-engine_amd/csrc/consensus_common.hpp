@@ -2,8 +2,9 @@
 // (consensus.hip: the seg and long-market kernels and the choice among the short-market
 // kernels; consensus_lane.hip: the lane-per-market kernels for n <= 32, their shared pieces in
 // consensus_lane.hpp; consensus_tab.hip: the LDS-table kernel for contiguous short markets;
-// consensus_wide.hip: 64 < n <= 4096; consensus_api.hip: the C entries that pick among them;
-// plan.hip: the planners).
+// consensus_wide.hip: 64 < n <= 4096, its sort network in wide_sort.hpp and its chain loops in
+// ordered_chain.hpp; consensus_api.hip: the C entries that pick among them; plan.hip: the
+// planners), and the few device pieces every one of them writes the same way.
 #pragma once
 #pragma clang fp contract(off)
 
@@ -74,6 +75,26 @@ constexpr int kBitsLds = 512;  // present bitmask words staged in LDS (S <= 1638
 
 __device__ __forceinline__ bool is_present(const uint32_t* bits, int s) {
   return ((bits[s >> 5] >> (s & 31)) & 1u) != 0;
+}
+
+// ---- results every consensus kernel writes the same way ------------------------------------
+// the four per-market values (core.py:131-133: no weight, no consensus); err_idx stays with
+// the caller
+__device__ __forceinline__ void store_market(const ConsArgs& a, int64_t mk, double total, double ws, double cs,
+                                             int j) {
+  const bool null_ = (total == 0.0);
+  a.consensus[mk] = null_ ? 0.0 : ws / total;
+  a.confidence[mk] = null_ ? 0.0 : cs / total;
+  a.total_weight[mk] = total;
+  a.n_unique[mk] = j;
+}
+// bit 31 of usid: the source is not a key of the reliability dict (core.py:167-170); `word` is
+// the present word of sid
+__device__ __forceinline__ unsigned cold_flag(uint32_t word, int sid) {
+  return (((word >> (sid & 31)) & 1u) == 0u) ? 0x80000000u : 0u;
+}
+__device__ __forceinline__ double norm_weight(double w, double tot) {  // core.py:151
+  return (tot > 0.0) ? w / tot : 0.0;
 }
 
 // Batcher odd-even merge sort network for N (power of two) keys, generated at compile

@@ -142,17 +142,7 @@ __device__ __forceinline__ void walk_pin(Walk& k) {
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// ---- results ---------------------------------------------------------------------------------
-// per-market results (lane = market: coalesced); err_idx stays with the caller
-__device__ __forceinline__ void store_market(const ConsArgs& a, int64_t mk, double total, double ws, double cs,
-                                             int j) {
-  const bool null_ = (total == 0.0);  // core.py:131-133
-  a.consensus[mk] = null_ ? 0.0 : ws / total;
-  a.confidence[mk] = null_ ? 0.0 : cs / total;
-  a.total_weight[mk] = total;
-  a.n_unique[mk] = j;
-}
-
+// ---- results (store_market, cold_flag, norm_weight: consensus_common.hpp) --------------------
 struct Unique {
   unsigned sid;
   int slot;
@@ -166,13 +156,6 @@ __device__ __forceinline__ Unique unpack_unique(unsigned pk) {
 __device__ __forceinline__ uint32_t present_word(const uint32_t* sBits, const uint32_t* pbits, bool bits_in_lds,
                                                  unsigned sid) {
   return bits_in_lds ? sBits[sid >> 5] : pbits[sid >> 5];
-}
-// bit 31 of usid: the source is not a key of the reliability dict (core.py:167-170)
-__device__ __forceinline__ unsigned cold_flag(uint32_t word, int sid) {
-  return (((word >> (sid & 31)) & 1u) == 0u) ? 0x80000000u : 0u;
-}
-__device__ __forceinline__ double norm_weight(double w, double tot) {  // core.py:151
-  return (tot > 0.0) ? w / tot : 0.0;
 }
 // 8-B usid pairs and 16-B weight / nweight pairs can be stored: the arrays are aligned and
 // every row of the tile starts at an even signal

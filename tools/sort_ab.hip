@@ -1,6 +1,6 @@
 // Sort A/B for the C3 wide kernel (verdict r04 item 1), not product code: 4096-key blocks
 // (one workgroup of 8 waves per block, R = 8 keys per thread) sorted by
-//   bitonic  the shipped register network, consensus_wide.hip wide_sort<8, 8, 8> (keys
+//   bitonic  the shipped register network, wide_sort.hpp wide_sort<8, 8, 8> (keys
 //            sid << 12 | i, striped input i = c*NT + t, blocked output q = t*R + r), and
 //   radix    a stable LSD radix sort of the same keys on the sid bits only (the index bits
 //            ride along), 4-bit digits, per-thread packed 16-bit digit counters in LDS
@@ -20,7 +20,7 @@
 #include <random>
 #include <vector>
 
-#include "consensus_wide.hip"
+#include "wide_sort.hpp"
 
 using namespace bce;
 

@@ -84,10 +84,10 @@ VARIANTS = {
     "xsort2": [("consensus_wide.hip", "  wide_sort<NN, NW, R>(key, sX, t, lane);\n",
                 "  wide_sort<NN, NW, R>(key, sX, t, lane);\n  wide_sort<NN, NW, R>(key, sX, t, lane);\n")],
     # no relconf / present-bit gathers (constant rows)
-    "xnogather": [("consensus_wide.hip", "rc[i] = a.relconf[sids[i]];", "rc[i] = make_double2(0.5 + 1e-9 * sids[i], 0.25);"),
-                  ("consensus_wide.hip", "pwd[i] = a.pbits[sids[i] >> 5];", "pwd[i] = 0xFFFFFFFFu;")],
+    "xnogather": [("consensus_wide.hip", "g.rc = c.a.relconf[g.sid];", "g.rc = make_double2(0.5 + 1e-9 * g.sid, 0.25);"),
+                  ("consensus_wide.hip", "g.pwd = c.a.pbits[g.sid >> 5];", "g.pwd = 0xFFFFFFFFu;")],
     # no normalizedWeight phase
-    "xnonw": [("consensus_wide.hip", "  if (a.nweight) {  // core.py:151", "  if (false) {  // core.py:151")],
+    "xnonw": [("consensus_wide.hip", "  if (!a.nweight) return;  // not requested", "  return;  // ablated")],
 }
 ABLATIONS = {"xsort2", "xnogather", "xnonw"}
 
