@@ -278,8 +278,8 @@ def score_sources(plan: ScorePlan, prob: torch.Tensor, outcome: torch.Tensor,
     return score(plan, prob.to(torch.float64), outcome, valid=valid, base=consensus, **kw)
 
 
-def walk_sweep(plan: WalkPlan, table: "ReliabilityTable", market_time_us: torch.Tensor, *, offsets: torch.Tensor,
-               prob: torch.Tensor, half_life_days: Sequence[float], min_rel: Sequence[float],
+def walk_sweep(plan: WalkPlan, table: "ReliabilityTable", market_time_us: Optional[torch.Tensor] = None, *,
+               offsets: torch.Tensor, prob: torch.Tensor, half_life_days: Sequence[float], min_rel: Sequence[float],
                score_plan: Optional[ScorePlan] = None, keep_consensus: bool = False, all_present: bool = True,
                mode: str = "exact", long_min: Optional[int] = None, chunk_bits: Optional[int] = None,
                n_bins: int = 10, eps: float = 1e-15, **consensus_kwargs):
@@ -290,6 +290,7 @@ def walk_sweep(plan: WalkPlan, table: "ReliabilityTable", market_time_us: torch.
     ``(half_life_days[i], min_rel[j])`` (row-major, ``min_rel`` fastest) runs bce_walk_read from
     that trace into a second table, :func:`consensus` and :func:`score`.  The table is never
     written; the read table, the consensus outputs and the scoring scratch are allocated once.
+    ``market_time_us`` as :func:`walk_forward`: None for a lagged plan, which has its own times.
     Returns ``(scores, consensus)``: a :class:`ScoreResult` with a leading grid dimension
     ``[len(half_life_days) * len(min_rel), G, ...]`` over ``score_plan`` (default: one group of all
     markets) and, with ``keep_consensus``, the fp64 ``[K, M]`` consensus and bool ``[K, M]``

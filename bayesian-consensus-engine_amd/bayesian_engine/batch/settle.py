@@ -18,10 +18,11 @@ SETTLE_LONG_OFF = 1 << 62
 
 
 def _settle_order(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
-                  n_sources: int):
+                  n_sources: int, market_rank: Optional[torch.Tensor] = None):
     """The integer half of :meth:`SettlePlan.build` (any device, no kernel): checks the shapes,
-    lists the signals of markets with ``outcome >= 0`` in CSR order and sorts them by ``sid``
-    keeping that order inside a source.  Returns ``(market, perm, key, total, start, order,
+    lists the signals of markets with ``outcome >= 0`` in CSR order -- with ``market_rank``
+    int64[M], in ``(market_rank[market], position)`` order -- and sorts them by ``sid`` keeping
+    that order inside a source.  Returns ``(market, perm, key, total, start, order,
     lens_desc)``: the market of every signal (int32[N]), the signal index and clamped sid of every
     sorted position, the chain length and bit offset per source, the touched sources longest
     chain first and their lengths."""
@@ -31,6 +32,10 @@ def _settle_order(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, 
     i64 = dict(dtype=torch.int64, device=dev)
     market = torch.repeat_interleave(torch.arange(M, **i64), lens, output_size=Nsig)
     idx = torch.nonzero(outcome[market] >= 0).flatten()  # ascending: market, then position
+    if market_rank is not None:
+        if market_rank.dtype != torch.int64 or market_rank.dim() != 1 or market_rank.numel() != M:
+            raise ValueError(f"market_rank must be int64 with one entry per market ({M})")
+        idx = idx[torch.sort(market_rank[market[idx]], stable=True).indices]
     key = sid[idx].to(torch.int32).clamp(0, S - 1)
     key, p = torch.sort(key, stable=True)
     perm = idx[p]
@@ -48,7 +53,8 @@ class SettlePlan:
     """A batch of resolved markets compiled for :func:`settle`: one correctness bit per signal
     of a market with ``outcome >= 0`` -- ``(probability >= 0.5) == outcome``, market.py:298-301 --
     the bits of one source contiguous and in the reference's loop order (market ascending, then
-    position in the market).  ``bits`` u64[ceil(n_bits / 64)] (as int64), ``start`` int64[S+1]
+    position in the market; with ``market_rank``, the rank of the market ascending).  ``bits``
+    u64[ceil(n_bits / 64)] (as int64), ``start`` int64[S+1]
     (bit offset of every source's chain), ``order`` int32[T] (the touched sources, longest chain
     first), ``total`` / ``correct`` int64[S] (chain length and its popcount: the
     summarize_sources counts, market.py:293-304).  Reusable: the same plan settles the domain and
@@ -70,14 +76,25 @@ class SettlePlan:
 
     @classmethod
     def build(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
-              n_sources: int, check: bool = True) -> "SettlePlan":
+              n_sources: int, check: bool = True, market_rank: Optional[torch.Tensor] = None) -> "SettlePlan":
         """Compile ``(offsets, sid, prob)`` with ``outcome`` int8[M] (-1 unresolved, 0, 1).  The
         ordering is a stable torch sort by ``sid``; the bits and ``correct`` are one launch of
         bce_settle_compile.  Synchronises (once per batch).  A ``sid`` outside ``[0, n_sources)``
         is clamped and raises :class:`BCEError` like ``consensus(check=True)`` (``check=False``
         leaves the device fault word for a later ``_native.check_faults``); 2^31 markets or
-        sources, an ``outcome`` of the wrong length or dtype, ``ValueError``."""
-        market, perm, key, total, start, order, lens_desc = _settle_order(offsets, sid, prob, outcome, n_sources)
+        sources, an ``outcome`` of the wrong length or dtype, ``ValueError``.
+
+        ``market_rank`` int64[M]: the bits of a source are ordered by ``(market_rank[market],
+        position)`` instead of ``(market, position)`` -- the order the markets settle in when
+        that is not their index order (:meth:`WalkPlan.build_lagged`)."""
+        return cls._compile(offsets, sid, prob, outcome, n_sources, check, market_rank)[0]
+
+    @classmethod
+    def _compile(cls, offsets, sid, prob, outcome, n_sources, check, market_rank):
+        """:meth:`build`: ``(plan, market, perm)`` with the market of every signal (int32[N]) and
+        the signal of every chain bit in chain order (int64[n_bits])."""
+        market, perm, key, total, start, order, lens_desc = _settle_order(offsets, sid, prob, outcome, n_sources,
+                                                                          market_rank)
         M, Nsig, S, Np = offsets.numel() - 1, sid.numel(), int(n_sources), perm.numel()
         dev = offsets.device
         L = N.require_gpu()
@@ -91,7 +108,7 @@ class SettlePlan:
                 "bce_settle_compile")
         if check:
             N.check_faults(dev, "settle compile")
-        return cls(bits, start, order, total, correct, Np, S, lens_desc)
+        return cls(bits, start, order, total, correct, Np, S, lens_desc), market, perm
 
     def chunks(self, long_min: int, chunk_bits: int):
         """``(n_long, chunk_start, n_chunks)`` of the long path for these parameters (cached)."""

@@ -106,7 +106,12 @@ class WalkPlan:
     source: the chain position whose before-state the query reads, 0 <= qpos <= chain length),
     ``qentry`` int32[E] (the entry a query answers), ``qlast`` int32[E] (by entry: the market of
     chain bit ``qpos - 1``, -1 when ``qpos == 0``) and ``slast`` int64[S] (the last resolved
-    market of every source, -1 where none).  ``n_clamped``: sids outside ``[0, n_sources)``."""
+    market of every source, -1 where none).  ``n_clamped``: sids outside ``[0, n_sources)``.
+
+    A plan from :meth:`build_lagged` (``lagged``) carries a forecast and a resolve time per market
+    (DESIGN §4.21): its chains are in (resolve time, market, position) order, ``qpos`` counts the
+    bits resolved before the entry's forecast, ``qlast`` / ``slast`` are the markets of bit
+    ``qpos - 1`` and of the chain's last bit, and the walk takes its times from the plan."""
 
     settle: SettlePlan
     pairs: PairPlan
@@ -117,6 +122,12 @@ class WalkPlan:
     slast: torch.Tensor
     n_clamped: int
     outcome: Optional[torch.Tensor] = None  # int8[M], as given to build (scoring reads it)
+    forecast_time_us: Optional[torch.Tensor] = None  # int64[M], build_lagged only
+    resolve_time_us: Optional[torch.Tensor] = None   # int64[M], read where outcome >= 0
+
+    @property
+    def lagged(self) -> bool:
+        return self.forecast_time_us is not None
 
     @property
     def total(self) -> torch.Tensor:
@@ -154,6 +165,89 @@ class WalkPlan:
             raise N.BCEError(f"walk plan: {n_clamped} sid outside [0, {int(n_sources)})")
         return cls(splan, pairs, qstart, qpos, qentry, qlast, slast, n_clamped, outcome.contiguous())
 
+    @classmethod
+    def build_lagged(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
+                     n_sources: int, forecast_time_us: torch.Tensor, resolve_time_us: torch.Tensor,
+                     check: bool = True) -> "WalkPlan":
+        """:meth:`build` for markets that are forecast at one time and settle at a later one:
+        market m is read at ``forecast_time_us[m]`` and, if ``outcome[m] >= 0``, its updates run
+        at ``resolve_time_us[m]`` -- the reference as an event loop sorted by (time, market,
+        forecast before resolution).  Markets are given in forecast order.  ``ValueError`` (from
+        torch checks on whatever device the tensors are on, before the library is touched) unless
+        both are int64[M], the forecast times do not decrease and ``resolve >= forecast`` for
+        every resolved market; resolve times of unresolved markets are ignored.
+
+        The chains are compiled in (resolve time, market, position) order (one stable sort over M
+        for the rank, :meth:`SettlePlan.build` with ``market_rank``); the queries are the entries
+        in (source, market) order as in :meth:`build`, and one launch of bce_walk_lag_queries
+        bisects every query's visible prefix.  With ``resolve == forecast`` the plan equals
+        :meth:`build`'s, array for array."""
+        M, _, S, _, _ = _check_csr(offsets, sid, n_sources, outcome=outcome, values=False)
+        _check_lag_times(forecast_time_us, resolve_time_us, outcome, M)
+        dev = offsets.device
+        i64 = dict(dtype=torch.int64, device=dev)
+        clamped = sid.to(torch.int32).clamp(0, S - 1)
+        n_clamped = int((clamped != sid).sum())
+        pairs = PairPlan.build(offsets, clamped, prob, S)  # checks offsets / prob
+        forecast = forecast_time_us.contiguous()
+        resolve = resolve_time_us.contiguous()
+        # the rank of every resolved market by (resolve time, market); the others behind them
+        key = torch.where(outcome >= 0, resolve, torch.full_like(resolve, torch.iinfo(torch.int64).max))
+        rank = torch.empty(M, **i64)
+        rank[torch.sort(key, stable=True).indices] = torch.arange(M, **i64)
+        L = N.require_gpu()
+        splan, market, perm = SettlePlan._compile(offsets, sid, prob, outcome, n_sources, check, rank)
+        bit_market = market[perm].contiguous()
+        E = pairs.n_entries
+        usid = pairs.usid[:E].to(torch.int64)
+        qentry = torch.sort(usid, stable=True).indices.to(torch.int32).contiguous()  # (source, market) order
+        qstart = torch.zeros(S + 1, **i64)
+        qstart[1:] = torch.cumsum(torch.bincount(usid, minlength=S), 0)
+        qpos = torch.empty(E, **i64)
+        qlast = torch.full((E,), -1, dtype=torch.int32, device=dev)
+        slast = torch.empty(S, **i64)
+        ent = lambda t: N.ptr(t if E else None)  # noqa: E731
+        N.check(L.bce_walk_lag_queries(E, ent(qentry), ent(pairs.usid), ent(pairs.emarket), E, N.ptr(splan.start), S,
+                                       N.ptr(bit_market if splan.n_bits else None), splan.n_bits,
+                                       N.ptr(forecast if M else None), N.ptr(resolve if M else None), M, ent(qpos),
+                                       ent(qlast), N.ptr(slast), N.stream(dev)), "bce_walk_lag_queries")
+        if check:
+            N.check_faults(dev, "walk lag queries")
+            if n_clamped:  # in an unresolved market: the settlement compile does not see it
+                raise N.BCEError(f"walk plan: {n_clamped} sid outside [0, {int(n_sources)})")
+        return cls(splan, pairs, qstart, qpos, qentry, qlast, slast, n_clamped, outcome.contiguous(), forecast,
+                   resolve)
+
+
+def _check_lag_times(forecast_time_us: torch.Tensor, resolve_time_us: torch.Tensor, outcome: torch.Tensor,
+                     M: int) -> None:
+    """The validity of a lagged batch's times (torch only, any device)."""
+    for name, t in (("forecast_time_us", forecast_time_us), ("resolve_time_us", resolve_time_us)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or t.numel() != M:
+            raise ValueError(f"{name} must be int64 with one entry per market ({M})")
+    if forecast_time_us.device != outcome.device or resolve_time_us.device != outcome.device:
+        raise ValueError("forecast_time_us / resolve_time_us must be on the batch's device")
+    if M > 1 and bool((forecast_time_us[1:] < forecast_time_us[:-1]).any()):
+        at = int(torch.nonzero(forecast_time_us[1:] < forecast_time_us[:-1])[0]) + 1
+        raise ValueError(f"forecast times must not decrease: market {at} is forecast before market {at - 1}")
+    early = (outcome >= 0) & (resolve_time_us < forecast_time_us)
+    if bool(early.any()):
+        at = int(torch.nonzero(early)[0])
+        raise ValueError(f"market {at} resolves before it is forecast")
+
+
+def _walk_times(plan: WalkPlan, market_time_us: Optional[torch.Tensor]):
+    """``(stamp, now)``: the time a market's updates are stamped with and the time it is read at
+    -- the plan's resolve and forecast times, or ``market_time_us`` twice."""
+    if plan.lagged:
+        if market_time_us is not None:
+            raise ValueError("a lagged plan carries its own times: market_time_us must be None")
+        return plan.resolve_time_us, plan.forecast_time_us
+    if market_time_us is None:
+        raise ValueError("market_time_us is needed: the plan has no times of its own (WalkPlan.build_lagged does)")
+    _check_market_time(market_time_us, plan.pairs.n_markets)
+    return market_time_us, market_time_us
+
 
 class _ConsensusFields:
     """For a result that holds a :class:`ConsensusResult` as ``result``: its fields, directly."""
@@ -182,13 +276,13 @@ class WalkResult(_ConsensusFields):
     correct: torch.Tensor
 
 
-def walk_trace(plan: WalkPlan, table: "ReliabilityTable", market_time_us: torch.Tensor, *,
+def walk_trace(plan: WalkPlan, table: "ReliabilityTable", market_time_us: Optional[torch.Tensor] = None, *,
                all_present: bool = True, long_min: Optional[int] = None, chunk_bits: Optional[int] = None,
                half_life_days: float = DECAY_HALF_LIFE_DAYS, min_rel: float = DECAY_MINIMUM):
     """The read side of :func:`walk_forward` alone (bce_settle_trace + bce_walk_read): the
     consensus table over the entry index -- every entry's ``get_reliability(apply_decay=True)`` at
     its market's time, after the earlier markets were settled -- and ``scope_present`` u8[E].
-    The table is not written."""
+    The table is not written.  ``market_time_us``: as :func:`walk_forward`."""
     E = plan.pairs.n_entries
     dev = table.rel.device
     relconf, bits, exists = _entry_buffers(E, dev)  # relconf: the trace, decayed in place
@@ -197,35 +291,40 @@ def walk_trace(plan: WalkPlan, table: "ReliabilityTable", market_time_us: torch.
     return SourceTable(relconf, bits, range(E)), exists[:E]  # "names": the entry indices
 
 
-def _walk_settle_trace(plan: WalkPlan, table: "ReliabilityTable", market_time_us: torch.Tensor,
+def _walk_settle_trace(plan: WalkPlan, table: "ReliabilityTable", market_time_us: Optional[torch.Tensor],
                        trace: torch.Tensor, long_min: Optional[int], chunk_bits: Optional[int]) -> None:
     """:func:`_settle_trace` of ``plan`` from ``table`` into ``trace`` [E, 2]; checks the table
     and the times."""
+    _walk_times(plan, market_time_us)
     N.require_gpu()
     sp, pp = plan.settle, plan.pairs
     _check_table(table.rel, table.conf, table.t_us, table.present, sp.n_sources)
-    _check_market_time(market_time_us, pp.n_markets)
     _settle_trace(sp, plan.queries, table.rel, table.conf, table.present, pp.n_entries, trace, long_min,
                   chunk_bits, N.stream(table.rel.device))
 
 
-def _walk_read(plan: WalkPlan, table: "ReliabilityTable", market_time_us: torch.Tensor, trace: torch.Tensor,
-               relconf: torch.Tensor, bits: torch.Tensor, exists: torch.Tensor, all_present: bool,
+def _walk_read(plan: WalkPlan, table: "ReliabilityTable", market_time_us: Optional[torch.Tensor],
+               trace: torch.Tensor, relconf: torch.Tensor, bits: torch.Tensor, exists: torch.Tensor, all_present: bool,
                half_life_days: float, min_rel: float) -> None:
-    """bce_walk_read from ``trace`` into ``relconf`` (may be ``trace`` itself) / ``bits`` / ``exists``."""
+    """bce_walk_read (a lagged plan: bce_walk_read_lag) from ``trace`` into ``relconf`` (may be
+    ``trace`` itself) / ``bits`` / ``exists``."""
     L = N.require_gpu()
     sp, pp = plan.settle, plan.pairs
     S, E, M = sp.n_sources, pp.n_entries, pp.n_markets
-    mtime = market_time_us.contiguous()
+    stamp, now = _walk_times(plan, market_time_us)
     ent = lambda t: N.ptr(t if E else None)  # noqa: E731
-    N.check(L.bce_walk_read(E, ent(pp.usid), ent(pp.emarket), ent(plan.qlast), N.ptr(trace),
-                            N.ptr(mtime if M else None), M, N.ptr(table.rel), N.ptr(table.conf), N.ptr(table.t_us), N.ptr(table.present), S,
-                            float(half_life_days), float(min_rel), DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE,
-                            int(not all_present), int(plan.n_clamped > 0), N.ptr(relconf), N.ptr(bits),
-                            N.ptr(exists), N.stream(table.rel.device)), "bce_walk_read")
+    if plan.lagged:
+        read, times = L.bce_walk_read_lag, (N.ptr(stamp if M else None), N.ptr(now if M else None))
+    else:
+        read, times = L.bce_walk_read, (N.ptr(now.contiguous() if M else None),)
+    N.check(read(E, ent(pp.usid), ent(pp.emarket), ent(plan.qlast), N.ptr(trace), *times, M, N.ptr(table.rel),
+                 N.ptr(table.conf), N.ptr(table.t_us), N.ptr(table.present), S, float(half_life_days), float(min_rel),
+                 DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE, int(not all_present), int(plan.n_clamped > 0),
+                 N.ptr(relconf), N.ptr(bits), N.ptr(exists), N.stream(table.rel.device)),
+            "bce_walk_read_lag" if plan.lagged else "bce_walk_read")
 
 
-def walk_forward(plan: WalkPlan, table: "ReliabilityTable", market_time_us: torch.Tensor, *,
+def walk_forward(plan: WalkPlan, table: "ReliabilityTable", market_time_us: Optional[torch.Tensor] = None, *,
                  offsets: torch.Tensor, prob: torch.Tensor, all_present: bool = True, mode: str = "exact",
                  long_min: Optional[int] = None, chunk_bits: Optional[int] = None, commit: bool = True,
                  **consensus_kwargs) -> WalkResult:
@@ -238,6 +337,11 @@ def walk_forward(plan: WalkPlan, table: "ReliabilityTable", market_time_us: torc
     undecayed.  ``all_present=False`` sets the cold bit of ``usid`` where no row existed at read
     time (``present == 0`` in the start table and no earlier update in the batch).
 
+    A plan from :meth:`WalkPlan.build_lagged` takes its times from the plan (``market_time_us``
+    stays None; passing one as well, or none for an ordinary plan, ``ValueError``): market m is
+    read at its forecast time, settled at its resolve time, and every state is stamped with the
+    resolve time of the market of its last bit.
+
     :func:`walk_trace` builds the consensus table over the entries, :func:`consensus` runs
     unchanged with ``plan.pairs.esid`` as the ranks (``mode`` and ``consensus_kwargs`` go to it;
     ``bins=`` is its length-bin :class:`Plan`).  ``commit=True`` also leaves the table settled:
@@ -247,16 +351,16 @@ def walk_forward(plan: WalkPlan, table: "ReliabilityTable", market_time_us: torc
     sp, pp = plan.settle, plan.pairs
     if offsets.numel() - 1 != pp.n_markets or prob.numel() != pp.esid.numel():
         raise ValueError("offsets / prob are not the batch the plan was built from")
+    stamp, _ = _walk_times(plan, market_time_us)
     wtable, exists = walk_trace(plan, table, market_time_us, all_present=all_present, long_min=long_min,
                                 chunk_bits=chunk_bits)
     res = consensus(offsets, pp.esid, prob.to(torch.float64), wtable, mode=mode, **_bins_as_plan(consensus_kwargs))
     if commit and sp.n_touched:
-        _commit_chains(sp, table.rel, table.conf, table.t_us, table.present, plan.slast, market_time_us, long_min,
-                       chunk_bits)
+        _commit_chains(sp, table.rel, table.conf, table.t_us, table.present, plan.slast, stamp, long_min, chunk_bits)
     return WalkResult(res, plan, exists, sp.total, sp.correct)
 
 
-def _table_walk_forward(self, plan: WalkPlan, market_time_us: torch.Tensor, **kw) -> WalkResult:
+def _table_walk_forward(self, plan: WalkPlan, market_time_us: Optional[torch.Tensor] = None, **kw) -> WalkResult:
     """:func:`walk_forward` on this table (a domain or the global scope)."""
     return walk_forward(plan, self, market_time_us, **kw)
 

@@ -548,7 +548,7 @@ class CrossMarketAggregator:
 
     def walk_forward(self, store, patterns: Optional[List[str]] = None, domain: Optional[str] = None,
                      dry_run: bool = False, device_match: Optional[bool] = None, domain_of=None,
-                     update_global: bool = False, market_scope: bool = False):
+                     update_global: bool = False, market_scope: bool = False, lagged: bool = False):
         """A back-test over the store's history: every market with signals (selected as
         reestimate_sources selects them), ordered by (time, store position) -- ``resolved_at`` for
         a RESOLVED market with an outcome, ``created_at`` otherwise -- is scored with the
@@ -563,13 +563,25 @@ class CrossMarketAggregator:
         global -> cold start and settled at the scope of its own domain, ``update_global`` as
         ``update_reliability`` takes it (``store.walk_forward_namespaced``); ``market_scope=True``
         passes ``str(market.id)`` so that seeded (source, market) rows are read first.  Without
-        ``domain_of`` the two flags are not used."""
+        ``domain_of`` the two flags are not used.
+
+        ``lagged=True`` keeps a market's two events apart: every market is forecast at
+        ``created_at`` and a resolved one settled at ``resolved_at``, the order is (``created_at``,
+        store position), and a market reads only the outcomes that had arrived by its forecast
+        (``store.walk_forward(resolve_times=)``).  A resolved market whose ``resolved_at`` is
+        missing or earlier than its ``created_at`` is a ``ValueError`` that names it.  The lagged
+        walk is single-scope: together with ``domain_of=``, ``ValueError``."""
+        if lagged and domain_of is not None:
+            raise ValueError("lagged=True walks one scope: it cannot be combined with domain_of=")
         if domain_of is not None:
             if domain is not None:
                 raise ValueError("domain= (one for the batch) and domain_of= (one per market) exclude each other")
             domain_of = _domain_fn(domain_of)
-        keyed, batch_markets, stamps = self._walk_history(patterns, device_match)
-        if domain_of is not None:
+        keyed, batch_markets, stamps, resolve_stamps = self._walk_history(patterns, device_match, lagged)
+        if lagged:
+            results, summary = store.walk_forward(batch_markets, stamps, domain=domain, dry_run=dry_run,
+                                                  resolve_times=resolve_stamps)
+        elif domain_of is not None:
             results, summary = store.walk_forward_namespaced(
                 batch_markets, stamps, domains=[domain_of(m) for _, _, m, _ in keyed],
                 market_ids=[str(m.id) for _, _, m, _ in keyed] if market_scope else None,
@@ -582,23 +594,33 @@ class CrossMarketAggregator:
             out[str(m.id)] = r
         return out, summary
 
-    def _walk_history(self, patterns: Optional[List[str]], device_match: Optional[bool]):
-        """The markets of a back-test in walk order: ``(keyed, batch_markets, stamps)`` with
-        ``keyed`` = ``(time_us, store position, market, resolved)`` sorted by (time, position),
-        ``batch_markets`` the ``(signals, outcome or None)`` pairs and ``stamps`` the ISO times."""
+    def _walk_history(self, patterns: Optional[List[str]], device_match: Optional[bool], lagged: bool = False):
+        """The markets of a back-test in walk order: ``(keyed, batch_markets, stamps,
+        resolve_stamps)`` with ``keyed`` = ``(time_us, store position, market, resolved)`` sorted
+        by (time, position), ``batch_markets`` the ``(signals, outcome or None)`` pairs and
+        ``stamps`` the ISO times.  ``lagged``: the time is ``created_at`` for every market, and
+        ``resolve_stamps`` holds ``resolved_at`` of the resolved ones (else it is None)."""
         markets = self._select(None, patterns, device_match, with_signals=True)
         keyed = []
         for pos, m in enumerate(markets):
             resolved = m.status == MarketStatus.RESOLVED and m.outcome is not None
-            stamp = m.resolved_at if resolved and m.resolved_at else m.created_at
+            stamp = m.resolved_at if resolved and m.resolved_at and not lagged else m.created_at
             t = iso_to_us(stamp)
             if t == NO_TIMESTAMP:
                 raise ValueError(f"market {m.id}: no usable time ({stamp!r})")
+            if lagged and resolved:
+                r = iso_to_us(m.resolved_at) if m.resolved_at else NO_TIMESTAMP
+                if r == NO_TIMESTAMP:
+                    raise ValueError(f"market {m.id}: resolved without a usable resolved_at ({m.resolved_at!r})")
+                if r < t:
+                    raise ValueError(f"market {m.id}: resolved_at {m.resolved_at!r} is earlier than created_at "
+                                     f"{m.created_at!r}")
             keyed.append((t, pos, m, resolved))
         keyed.sort(key=lambda k: k[:2])
         batch_markets = [(m.signals, m.outcome if resolved else None) for _, _, m, resolved in keyed]
         stamps = [us_to_iso(t) for t, _, _, _ in keyed]
-        return keyed, batch_markets, stamps
+        resolve_stamps = [m.resolved_at if resolved else None for _, _, m, resolved in keyed] if lagged else None
+        return keyed, batch_markets, stamps, resolve_stamps
 
     def score_walk(self, results: Dict[str, Dict[str, Any]], pattern_lists: Optional[List[List[str]]] = None,
                    domain_of=None, n_bins: int = 10, sources: bool = True,
@@ -705,14 +727,14 @@ class CrossMarketAggregator:
 
     def sweep_decay(self, store, half_life_days, min_rel, patterns: Optional[List[str]] = None,
                     domain: Optional[str] = None, n_bins: int = 10,
-                    device_match: Optional[bool] = None) -> List["BacktestScore"]:
+                    device_match: Optional[bool] = None, lagged: bool = False) -> List["BacktestScore"]:
         """The back-test of ``walk_forward(store, patterns, domain, dry_run=True)`` for every point
         of a grid of decay parameters: one whole-history :class:`BacktestScore` per
         ``(half_life_days[i], min_rel[j])``, row-major (``params`` names the point).  The
         settlement trace does not depend on the decay parameters, so it runs once
         (``store.sweep_decay``, ``batch.walk_sweep``); nothing is written to the store.  The
         single-scope walk only: a history that spans domains (``walk_forward(domain_of=)``) is
-        not swept here."""
+        not swept here.  ``lagged`` as in ``walk_forward``."""
         if not isinstance(store, NamespacedReliabilityStore):
             raise TypeError(f"sweep_decay needs a NamespacedReliabilityStore (got {type(store).__name__})")
         try:
@@ -728,9 +750,10 @@ class CrossMarketAggregator:
         B = int(n_bins)
         if not 1 <= B <= batch.SCORE_MAX_BINS:
             raise ValueError(f"n_bins must be in [1, {batch.SCORE_MAX_BINS}] (got {n_bins})")
-        _, batch_markets, stamps = self._walk_history(patterns, device_match)
+        _, batch_markets, stamps, resolve_stamps = self._walk_history(patterns, device_match, lagged)
         params = [{"half_life_days": h, "min_rel": m} for h in hl for m in mr]
-        scores = store.sweep_decay(batch_markets, stamps, hl, mr, domain=domain, n_bins=B)
+        scores = store.sweep_decay(batch_markets, stamps, hl, mr, domain=domain, n_bins=B,
+                                   resolve_times=resolve_stamps)
         if scores is None:
             return [BacktestScore.empty(B, p) for p in params]
         flat = batch.ScoreResult(*(getattr(scores, k)[:, 0] for k in ("counts", "sums", "bin_n", "bin_pos", "bin_psum")))

@@ -88,6 +88,36 @@ def _outcome_codes(markets) -> np.ndarray:
     return np.array([-1 if o is None else (1 if o else 0) for _, o in markets], np.int8)
 
 
+def _walk_times_us(markets, times, resolve_times):
+    """``(forecast or market times, resolve times or None)`` of a walk as int64 microseconds.
+    ``resolve_times`` has one entry per market; those of unresolved markets are not looked at."""
+    times = list(times)
+    if len(times) != len(markets):
+        raise ValueError(f"times has {len(times)} entries for {len(markets)} markets")
+    as_us = lambda t: iso_to_us(t) if isinstance(t, str) else dt_to_us(t)  # noqa: E731
+    t_us = np.array([as_us(t) for t in times], np.int64)
+    if (t_us == NO_TIMESTAMP).any():
+        raise ValueError("a market time is empty or unparseable")
+    if resolve_times is None:
+        return t_us, None
+    resolve_times = list(resolve_times)
+    if len(resolve_times) != len(markets):
+        raise ValueError(f"resolve_times has {len(resolve_times)} entries for {len(markets)} markets")
+    r_us = np.array([0 if o is None else (NO_TIMESTAMP if r is None else as_us(r))
+                     for (_, o), r in zip(markets, resolve_times)], np.int64)
+    if (r_us == NO_TIMESTAMP).any():
+        raise ValueError("the resolve time of a resolved market is empty or unparseable")
+    return t_us, r_us
+
+
+def _walk_plan(off, sid, prob, outcome, n_sources, t_us, r_us, T):
+    """``(plan, market_time_us)`` as :func:`batch.walk_forward` takes them: a lagged plan with its
+    own times where resolve times are given."""
+    if r_us is None:
+        return batch.WalkPlan.build(off, sid, prob, outcome, n_sources), T(t_us)
+    return batch.WalkPlan.build_lagged(off, sid, prob, outcome, n_sources, T(t_us), T(r_us)), None
+
+
 def _walk_dicts(markets, offsets, names, res, pairs) -> list:
     """The per-market ``compute_consensus``-shaped dicts of a walk-forward result whose ``usid``
     holds entry indices of ``pairs``."""
@@ -374,7 +404,7 @@ class NamespacedReliabilityStore:
         return SettleSummary(records, global_records, total, correct)
 
     def walk_forward(self, markets: Sequence[tuple], times: Sequence, domain: Optional[str] = None,
-                     dry_run: bool = False):
+                     dry_run: bool = False, resolve_times: Optional[Sequence] = None):
         """The reference run online over a chronological batch, as ONE compiled batch
         (:func:`batch.walk_forward`): market i is scored by ``compute_consensus`` with every source
         fetched by ``get_reliability(sid, scope, apply_decay=True)`` at ``times[i]``, then, if its
@@ -385,14 +415,17 @@ class NamespacedReliabilityStore:
         domain.  The scope is loaded once (``load_table``), the sources interned in sorted()
         order, and the final rows of the touched sources written back with one ``executemany``
         unless ``dry_run``.  Returns ``(results, summary)``: one dict per market shaped like
-        ``compute_consensus``'s, and the :class:`SettleSummary` of the settled scope."""
+        ``compute_consensus``'s, and the :class:`SettleSummary` of the settled scope.
+
+        ``resolve_times`` (one entry per market, as ``times``; ignored for unresolved markets)
+        separates the two events of a market: it is scored at ``times[i]`` and its updates run,
+        and stamp the rows, at ``resolve_times[i]`` -- the reference as an event loop sorted by
+        (time, market, forecast before resolution), so a market does not see outcomes that had
+        not arrived when it was forecast.  ``times`` must then be in order and no resolve time
+        earlier than its market's time (``ValueError``); rows written back carry the resolve time
+        of their last settling market."""
         markets = [(list(signals), outcome) for signals, outcome in markets]
-        times = list(times)
-        if len(times) != len(markets):
-            raise ValueError(f"times has {len(times)} entries for {len(markets)} markets")
-        t_us = np.array([iso_to_us(t) if isinstance(t, str) else dt_to_us(t) for t in times], np.int64)
-        if (t_us == NO_TIMESTAMP).any():
-            raise ValueError("a market time is empty or unparseable")
+        t_us, r_us = _walk_times_us(markets, times, resolve_times)
         namespace, value, target = self._update_scope(domain)
         rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
         names = list(rank)
@@ -404,9 +437,9 @@ class NamespacedReliabilityStore:
         dev = N.device()
         T = batch.to_device(dev)
         off, prob = T(offsets), T(prob)
-        plan = batch.WalkPlan.build(off, T(sid), prob, T(outcome), len(names))
+        plan, mtime = _walk_plan(off, T(sid), prob, T(outcome), len(names), t_us, r_us, T)
         table = self._store.load_table(target, names, device=dev)
-        res = table.walk_forward(plan, T(t_us), offsets=off, prob=prob, validate=False)
+        res = table.walk_forward(plan, mtime, offsets=off, prob=prob, validate=False)
         N.check_faults(dev, "walk_forward")
         results = _walk_dicts(markets, offsets, names, res, plan.pairs)
         touched = sorted(int(x) for x in plan.settle.order.cpu().numpy())
@@ -421,20 +454,16 @@ class NamespacedReliabilityStore:
                                       {names[i]: int(correct[i]) for i in touched})
 
     def sweep_decay(self, markets: Sequence[tuple], times: Sequence, half_life_days: Sequence[float],
-                    min_rel: Sequence[float], domain: Optional[str] = None, n_bins: int = 10):
+                    min_rel: Sequence[float], domain: Optional[str] = None, n_bins: int = 10,
+                    resolve_times: Optional[Sequence] = None):
         """:meth:`walk_forward` as a dry run for every point of a grid of decay parameters, each
         scored against the batch's outcomes (:func:`batch.walk_sweep`: the settlement trace does
         not depend on the decay parameters and runs once).  Nothing is written.  Returns the
         :class:`batch.ScoreResult` of the whole history with a leading grid dimension
         ``[len(half_life_days) * len(min_rel), 1, ...]`` (``min_rel`` fastest), or None for a
-        history without signals."""
+        history without signals.  ``resolve_times`` as :meth:`walk_forward`."""
         markets = [(list(signals), outcome) for signals, outcome in markets]
-        times = list(times)
-        if len(times) != len(markets):
-            raise ValueError(f"times has {len(times)} entries for {len(markets)} markets")
-        t_us = np.array([iso_to_us(t) if isinstance(t, str) else dt_to_us(t) for t in times], np.int64)
-        if (t_us == NO_TIMESTAMP).any():
-            raise ValueError("a market time is empty or unparseable")
+        t_us, r_us = _walk_times_us(markets, times, resolve_times)
         _, _, target = self._update_scope(domain)
         rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
         names = list(rank)
@@ -445,9 +474,9 @@ class NamespacedReliabilityStore:
         dev = N.device()
         T = batch.to_device(dev)
         off, prob = T(offsets), T(prob)
-        plan = batch.WalkPlan.build(off, T(sid), prob, T(_outcome_codes(markets)), len(names))
+        plan, mtime = _walk_plan(off, T(sid), prob, T(_outcome_codes(markets)), len(names), t_us, r_us, T)
         table = self._store.load_table(target, names, device=dev)
-        scores, _ = batch.walk_sweep(plan, table, T(t_us), offsets=off, prob=prob, half_life_days=half_life_days,
+        scores, _ = batch.walk_sweep(plan, table, mtime, offsets=off, prob=prob, half_life_days=half_life_days,
                                      min_rel=min_rel, n_bins=n_bins)
         N.check_faults(dev, "sweep_decay")
         return scores

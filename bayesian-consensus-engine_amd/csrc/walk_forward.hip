@@ -22,7 +22,12 @@
 //                       with the time of market qlast; qlast < 0 (no earlier bit, qpos == 0): the
 //                       start row, or the cold defaults where none exists.  Decays to the entry's
 //                       own market time and packs the consensus table over the entry index, the
-//                       present bits from one ballot per wave as pair_resolve_kernel does.
+//                       present bits from one ballot per wave as pair_resolve_kernel does.  With
+//                       resolution lag the stamp is the market's resolve time and the read time
+//                       its forecast time (bce_walk_read_lag); otherwise the two are one array.
+//   walk_lag_queries_kernel  one lane per query: the query order of a batch with resolution lag,
+//                       the visible prefix of the source's chain by bisection over the resolve
+//                       times of its bits.
 #include "reliability_update.hpp"
 #include "scope_lookup.hpp"
 #include "settle_walk.hpp"
@@ -177,7 +182,8 @@ struct WalkReadArgs {
   const int32_t* emarket;  // [E]
   const int32_t* qlast;    // [E] market of the last bit before the entry, -1: none
   const double2* trace;    // [E]
-  const int64_t* mtime;    // [M]
+  const int64_t* stamp;    // [M] the time a market's updates stamp updated_at with
+  const int64_t* now;      // [M] the time a market is read at (the same array without resolution lag)
   int64_t M;
   const double* rel;       // [S] the start table
   const double* conf;
@@ -218,7 +224,7 @@ __global__ __launch_bounds__(256) void walk_read_kernel(WalkReadArgs a) {
         const double2 st = a.trace[e];
         r = st.x;
         c = st.y;
-        t = a.mtime[ql];
+        t = a.stamp[ql];
         exists = true;
       } else if (a.present == nullptr || a.present[s]) {
         r = a.rel[s];
@@ -228,7 +234,7 @@ __global__ __launch_bounds__(256) void walk_read_kernel(WalkReadArgs a) {
       }
       if (exists) {  // reliability.py:114-123; a missing row is the cold start, undecayed
         DecayConst k = a.k;
-        k.now_us = a.mtime[m];
+        k.now_us = a.now[m];
         r = decayed(r, t, k, sExp);
       }
       a.relconf[e] = make_double2(r, c);
@@ -236,6 +242,96 @@ __global__ __launch_bounds__(256) void walk_read_kernel(WalkReadArgs a) {
     }
     store_present_bits(a.bits, base, a.E, in && (!a.mark_cold || exists));
     if (code && a.fault) atomicCAS(a.fault, 0, code);
+  }
+}
+
+// Resolution lag: market j is read at forecast[j] and settles at resolve[j] >= forecast[j].  A
+// source's chain holds its bits in (resolve time, market, position) order, and entry (j, s) sees
+// the bits whose market m has (resolve[m], m) < (forecast[j], j): a prefix of the chain, found by
+// bisection.  Without lag the prefix is "the markets before j" and the host counts it by a scan.
+struct LagQueryArgs {
+  int64_t Q;
+  const int32_t* qentry;      // [Q] the entry a query answers
+  const int32_t* usid;        // [E]
+  const int32_t* emarket;     // [E]
+  int64_t E;
+  const int64_t* start;       // [S + 1] bit range of every source's chain
+  int32_t S;
+  const int32_t* bit_market;  // [n_bits] the market of every chain bit, in chain order
+  int64_t n_bits;
+  const int64_t* forecast;    // [M]
+  const int64_t* resolve;     // [M] read for resolved markets only
+  int64_t M;
+  int64_t* qpos;              // [Q] by query, relative to the chain
+  int32_t* qlast;             // [E] by entry: the market of bit qpos - 1, -1: none
+  int64_t* slast;             // [S] the market of the chain's last bit, -1: none
+  int* fault;
+};
+
+// The chain of source s as a range of bit_market; false where start is no range inside [0, n_bits].
+__device__ __forceinline__ bool lag_chain(const LagQueryArgs& a, int32_t s, int64_t& b0, int64_t& b1) {
+  b0 = a.start[s];
+  b1 = a.start[s + 1];
+  return b0 >= 0 && b1 >= b0 && b1 <= a.n_bits;
+}
+
+// One lane per query, then one lane per source; every load is bounds-checked first, and a query
+// that meets bad input reads as "no earlier bit".  The position the bisection ends on has the
+// last probe that held on its left and the last that failed on its right -- bit qpos - 1 satisfies
+// the predicate and bit qpos does not, for any array -- so the neighbours need no second look;
+// what can go wrong is a range or an index, and those raise the fault word.
+__global__ __launch_bounds__(256) void walk_lag_queries_kernel(LagQueryArgs a) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  for (int64_t q = first; q < a.Q; q += stride) {
+    const int64_t e = a.qentry[q];
+    bool ok = e >= 0 && e < a.E;
+    int64_t pos = 0, last = -1;
+    if (ok) {
+      const int64_t s = a.usid[e], j = a.emarket[e];
+      int64_t b0 = 0, b1 = 0;
+      ok = s >= 0 && s < a.S && j >= 0 && j < a.M && lag_chain(a, (int32_t)s, b0, b1);
+      if (ok) {
+        const int64_t tj = a.forecast[j];
+        int64_t lo = b0, hi = b1;
+        while (lo < hi) {
+          const int64_t mid = lo + ((hi - lo) >> 1);
+          const int64_t m = a.bit_market[mid];
+          if (m < 0 || m >= a.M) {
+            ok = false;
+            break;
+          }
+          const int64_t tm = a.resolve[m];
+          if (tm < tj || (tm == tj && m < j)) {
+            lo = mid + 1;
+            last = m;  // the rightmost probe that held: bit lo - 1
+          } else {
+            hi = mid;
+          }
+        }
+        pos = lo - b0;
+      }
+      if (!ok) {
+        pos = 0;
+        last = -1;
+      }
+      a.qlast[e] = (int32_t)last;
+    }
+    a.qpos[q] = pos;
+    if (!ok && a.fault) atomicCAS(a.fault, 0, kFaultOffsets);
+  }
+  for (int64_t s = first; s < a.S; s += stride) {
+    int64_t b0, b1, last = -1;
+    bool ok = lag_chain(a, (int32_t)s, b0, b1);
+    if (ok && b1 > b0) {
+      last = a.bit_market[b1 - 1];
+      if (last < 0 || last >= a.M) {
+        ok = false;
+        last = -1;
+      }
+    }
+    a.slast[s] = last;
+    if (!ok && a.fault) atomicCAS(a.fault, 0, kFaultOffsets);
   }
 }
 
@@ -285,17 +381,19 @@ extern "C" int bce_settle_trace(const uint64_t* bits, int64_t n_bits, const int6
   return check_launch("trace_long_kernel");
 }
 
-extern "C" int bce_walk_read(int64_t n_entries, const int32_t* usid, const int32_t* emarket, const int32_t* qlast,
-                             const double* trace, const int64_t* market_time_us, int64_t n_markets,
-                             const double* rel, const double* conf, const int64_t* t_us, const uint8_t* present,
-                             int32_t n_sources, double half_life_days, double min_rel, double default_rel,
-                             double default_conf, int mark_cold, int sid_clamped, double* relconf,
-                             uint32_t* present_bits, uint8_t* exists, void* stream) {
+// bce_walk_read and bce_walk_read_lag: one kernel, the two time arrays equal without lag.
+static int walk_read_launch(int64_t n_entries, const int32_t* usid, const int32_t* emarket, const int32_t* qlast,
+                            const double* trace, const int64_t* stamp_time_us, const int64_t* market_time_us,
+                            int64_t n_markets, const double* rel, const double* conf, const int64_t* t_us,
+                            const uint8_t* present, int32_t n_sources, double half_life_days, double min_rel,
+                            double default_rel, double default_conf, int mark_cold, int sid_clamped,
+                            double* relconf, uint32_t* present_bits, uint8_t* exists, void* stream) {
   BCE_REQUIRE(n_entries >= 0 && n_markets >= 0 && n_sources > 0, "walk_read: bad shape");
   BCE_REQUIRE(n_entries < (1ll << 31) && n_markets < (1ll << 31), "walk_read: n_entries or n_markets >= 2^31");
   BCE_REQUIRE(n_markets > 0 || n_entries == 0, "walk_read: entries without markets");
   if (n_entries == 0 && !sid_clamped) return BCE_OK;
-  BCE_REQUIRE(n_entries == 0 || (usid && emarket && qlast && trace && market_time_us && rel && conf && t_us),
+  BCE_REQUIRE(n_entries == 0 ||
+                  (usid && emarket && qlast && trace && stamp_time_us && market_time_us && rel && conf && t_us),
               "walk_read: NULL argument");
   BCE_REQUIRE(n_entries == 0 || (relconf && present_bits), "walk_read: NULL output");
   BCE_REQUIRE((uintptr_t)relconf % 16 == 0 && (uintptr_t)trace % 16 == 0,
@@ -306,7 +404,8 @@ extern "C" int bce_walk_read(int64_t n_entries, const int32_t* usid, const int32
   a.emarket = emarket;
   a.qlast = qlast;
   a.trace = reinterpret_cast<const double2*>(trace);
-  a.mtime = market_time_us;
+  a.stamp = stamp_time_us;
+  a.now = market_time_us;
   a.M = n_markets;
   a.rel = rel;
   a.conf = conf;
@@ -324,4 +423,50 @@ extern "C" int bce_walk_read(int64_t n_entries, const int32_t* usid, const int32
   hipLaunchKernelGGL(walk_read_kernel, dim3((unsigned)(g < 1 ? 1 : (g < kWalkGridCap ? g : kWalkGridCap))), dim3(256),
                      0, as_stream(stream), a);
   return check_launch("walk_read_kernel");
+}
+
+extern "C" int bce_walk_read(int64_t n_entries, const int32_t* usid, const int32_t* emarket, const int32_t* qlast,
+                             const double* trace, const int64_t* market_time_us, int64_t n_markets,
+                             const double* rel, const double* conf, const int64_t* t_us, const uint8_t* present,
+                             int32_t n_sources, double half_life_days, double min_rel, double default_rel,
+                             double default_conf, int mark_cold, int sid_clamped, double* relconf,
+                             uint32_t* present_bits, uint8_t* exists, void* stream) {
+  return walk_read_launch(n_entries, usid, emarket, qlast, trace, market_time_us, market_time_us, n_markets, rel,
+                          conf, t_us, present, n_sources, half_life_days, min_rel, default_rel, default_conf,
+                          mark_cold, sid_clamped, relconf, present_bits, exists, stream);
+}
+
+extern "C" int bce_walk_read_lag(int64_t n_entries, const int32_t* usid, const int32_t* emarket,
+                                 const int32_t* qlast, const double* trace, const int64_t* stamp_time_us,
+                                 const int64_t* now_time_us, int64_t n_markets, const double* rel,
+                                 const double* conf, const int64_t* t_us, const uint8_t* present, int32_t n_sources,
+                                 double half_life_days, double min_rel, double default_rel, double default_conf,
+                                 int mark_cold, int sid_clamped, double* relconf, uint32_t* present_bits,
+                                 uint8_t* exists, void* stream) {
+  return walk_read_launch(n_entries, usid, emarket, qlast, trace, stamp_time_us, now_time_us, n_markets, rel, conf,
+                          t_us, present, n_sources, half_life_days, min_rel, default_rel, default_conf, mark_cold,
+                          sid_clamped, relconf, present_bits, exists, stream);
+}
+
+extern "C" int bce_walk_lag_queries(int64_t n_queries, const int32_t* qentry, const int32_t* usid,
+                                    const int32_t* emarket, int64_t n_entries, const int64_t* start,
+                                    int32_t n_sources, const int32_t* bit_market, int64_t n_bits,
+                                    const int64_t* forecast_time_us, const int64_t* resolve_time_us,
+                                    int64_t n_markets, int64_t* qpos, int32_t* qlast, int64_t* slast, void* stream) {
+  BCE_REQUIRE(n_queries >= 0 && n_entries >= 0 && n_bits >= 0 && n_markets >= 0 && n_sources > 0,
+              "walk_lag_queries: bad shape");
+  BCE_REQUIRE(n_entries < (1ll << 31) && n_markets < (1ll << 31), "walk_lag_queries: n_entries or n_markets >= 2^31");
+  BCE_REQUIRE(n_queries <= n_entries, "walk_lag_queries: more queries than entries");
+  BCE_REQUIRE(n_markets > 0 || (n_entries == 0 && n_bits == 0), "walk_lag_queries: entries or bits without markets");
+  BCE_REQUIRE(start && slast, "walk_lag_queries: NULL start or slast");
+  BCE_REQUIRE(n_bits == 0 || bit_market, "walk_lag_queries: NULL bit_market");
+  BCE_REQUIRE(n_queries == 0 || (qentry && usid && emarket && forecast_time_us && resolve_time_us && qpos && qlast),
+              "walk_lag_queries: NULL argument");
+  LagQueryArgs a{n_queries, qentry, usid, emarket, n_entries, start, n_sources, bit_market, n_bits,
+                 forecast_time_us, resolve_time_us, n_markets, qpos, qlast, slast, fault_word()};
+  const int64_t lanes = n_queries > n_sources ? n_queries : (int64_t)n_sources;
+  const int64_t g = (lanes + 255) / 256;
+  hipLaunchKernelGGL(walk_lag_queries_kernel, dim3((unsigned)(g < kWalkGridCap ? g : kWalkGridCap)), dim3(256), 0,
+                     as_stream(stream), a);
+  return check_launch("walk_lag_queries_kernel");
 }

@@ -469,6 +469,44 @@ int bce_walk_read(int64_t n_entries, const int32_t* usid, const int32_t* emarket
                   int mark_cold, int sid_clamped, double* relconf, uint32_t* present_bits, uint8_t* exists,
                   void* stream);
 
+/* ---- walk-forward with resolution lag: a forecast time and a resolve time per market ----------
+ * The reference as an event loop, the events sorted by (time, market, kind): F_m = (forecast_time_us
+ * [m], m, 0) scores market m with every source read at that time, R_m = (resolve_time_us[m], m, 1)
+ * runs update_reliability for every signal of a resolved market m and stamps updated_at with the
+ * resolve time.  Markets are given in forecast order (forecast times do not decrease) and
+ * resolve_time_us[m] >= forecast_time_us[m]; resolve times of unresolved markets are not read.  A
+ * source's chain then holds its bits in (resolve time, market, position) order, and entry (j, s)
+ * reads the state after the chain bits whose market m has resolve_time_us[m] < forecast_time_us[j],
+ * or the same time and m < j: a prefix of the chain.  bce_settle_compile, bce_settle_trace and
+ * bce_settle_apply run unchanged on that bit order.
+ *
+ * bce_walk_lag_queries: one lane per query q, e = qentry[q], s = usid[e], j = emarket[e]: the
+ * length of that prefix by bisection of [start[s], start[s + 1]) over bit_market[n_bits] (the
+ * market of every chain bit, in chain order) into qpos[q] (relative to the chain; ascending inside
+ * a source when the queries of a source ascend by market), and the market of bit qpos - 1 into
+ * qlast[e] (-1: none).  slast[s], for every source, is the market of its chain's last bit (-1: no
+ * bit).  With resolve == forecast these are the qpos / qlast / slast of the walk above.  A start
+ * that is no range inside [0, n_bits], a bit_market or emarket outside [0, n_markets), a usid
+ * outside [0, n_sources), a qentry outside [0, n_entries) raise the fault word; that query reads as
+ * qpos = 0, qlast = -1 (slast: -1) and nothing is read out of bounds.  The position a bisection
+ * ends on has a bit that satisfies the predicate on its left and one that does not on its right
+ * whatever the array holds, so the neighbours of qpos cannot contradict it and a chain whose bits
+ * are out of order is not detected: the order is the caller's (a stable sort on the host).
+ *
+ * bce_walk_read_lag: bce_walk_read with two time arrays: the traced state is stamped with
+ * stamp_time_us[qlast] and every state decayed to now_time_us[emarket] (the resolve and the
+ * forecast times).  One kernel serves both entries. */
+int bce_walk_lag_queries(int64_t n_queries, const int32_t* qentry, const int32_t* usid, const int32_t* emarket,
+                         int64_t n_entries, const int64_t* start, int32_t n_sources, const int32_t* bit_market,
+                         int64_t n_bits, const int64_t* forecast_time_us, const int64_t* resolve_time_us,
+                         int64_t n_markets, int64_t* qpos, int32_t* qlast, int64_t* slast, void* stream);
+int bce_walk_read_lag(int64_t n_entries, const int32_t* usid, const int32_t* emarket, const int32_t* qlast,
+                      const double* trace, const int64_t* stamp_time_us, const int64_t* now_time_us,
+                      int64_t n_markets, const double* rel, const double* conf, const int64_t* t_us,
+                      const uint8_t* present, int32_t n_sources, double half_life_days, double min_rel,
+                      double default_rel, double default_conf, int mark_cold, int sid_clamped, double* relconf,
+                      uint32_t* present_bits, uint8_t* exists, void* stream);
+
 /* ---- namespaced walk-forward: the market -> domain -> global fallback at every read ----------
  * The walk above with NamespacedReliabilityStore in the store's place: market m fetches every
  * source with get_reliability(s, market_id, domain_of(m), apply_decay=True)

@@ -16,11 +16,18 @@ resolved with a random outcome, market times one hour apart.
       WalkPlan.build + walk_forward on the same slice.  Reported as markets per second and not
       extrapolated to the whole batch.
 
+  (f) ``--lag``, in place of (a)-(e): the walk with a forecast and a resolve time per market
+      (WalkPlan.build_lagged), once with a lag drawn per market (0 to 72 hours, so the markets
+      settle out of forecast order) and once with ``resolve == forecast``, against the ordinary
+      plan and walk on the same batch: the build, the bce_walk_lag_queries launch alone, and the
+      whole walk_forward call.  Written to measurements/walk_lag.txt.
+
 Every timing is ``--calls`` back-to-back calls between two device synchronises on the host
 clock, each call that writes the table preceded by a reset from a pristine copy; the variants run
 interleaved, ``--reps`` times each.  All (b) variants must give identical tables.
 
     python tools/bench_walk_forward.py [--signals N] [--sources S] [--out measurements/walk_forward.txt]
+    python tools/bench_walk_forward.py --lag [--out measurements/walk_lag.txt]
 """
 from __future__ import annotations
 
@@ -122,6 +129,97 @@ def run_shape(name, off_h, sid_h, S, args, say):
     return ok, (off_h, sid_h, prob_h, outcome_h)
 
 
+def run_lag(name, off_h, sid_h, S, args, say):
+    """(f): build_lagged / bce_walk_lag_queries / walk_forward of a lagged plan against the ordinary ones."""
+    dev = torch.device("cuda", 0)
+    outcome_h, prob_h = outcomes_and_probs(off_h, sid_h, S, seed=17)
+    off, sid, prob, outcome = (torch.from_numpy(x).to(dev) for x in (off_h, sid_h, prob_h, outcome_h))
+    M, Nsig = len(off_h) - 1, len(sid_h)
+    forecast_h = T0 + HOUR * np.arange(M, dtype=np.int64)
+    lag_h = HOUR * np.random.default_rng(23).integers(0, 73, M)
+    forecast, drawn = torch.from_numpy(forecast_h).to(dev), torch.from_numpy(forecast_h + lag_h).to(dev)
+    calls = args.calls
+    builds = [("WalkPlan.build", lambda: batch.WalkPlan.build(off, sid, prob, outcome, S)),
+              ("build_lagged, resolve == forecast",
+               lambda: batch.WalkPlan.build_lagged(off, sid, prob, outcome, S, forecast, forecast)),
+              ("build_lagged, lag 0..72 h",
+               lambda: batch.WalkPlan.build_lagged(off, sid, prob, outcome, S, forecast, drawn))]
+    plans = [run() for _, run in builds]  # warm-up: code objects, torch sort workspaces
+    plain, zero, lagged = plans
+    E, nb = plain.pairs.n_entries, plain.settle.n_bits
+    moved = int((lagged.qpos != plain.qpos).sum())
+    say(f"== {name}: {M} markets, {Nsig} signals, {S} sources, {E} entries, {nb} chain bits; {calls} calls per "
+        f"timing; the drawn lag moves qpos of {moved} entries")
+    same_plan = torch.equal(zero.settle.bits, plain.settle.bits) and all(
+        torch.equal(getattr(zero, k), getattr(plain, k)) for k in ("qstart", "qpos", "qentry", "qlast", "slast"))
+    say(f"resolve == forecast gives the ordinary plan's arrays: {same_plan}")
+    times = {label: [] for label, _ in builds}
+    for _ in range(max(args.reps, 3)):
+        for label, run in builds:
+            times[label].append(timed(run)[0])
+    for label, _ in builds:
+        say(f"(f) {label:<46} ms: {fmt(times[label])}   (min {min(times[label]) * 1e3:.3f})")
+    # the query launch alone, on the arrays of either lagged plan
+    L = N.lib()
+    market = torch.repeat_interleave(torch.arange(M, dtype=torch.int32, device=dev), off[1:] - off[:-1])
+    launches = []
+    for label, p in (("resolve == forecast", zero), ("lag 0..72 h", lagged)):
+        # the market of every chain bit, restated: the signals by (source, resolve time, market, position)
+        t = p.resolve_time_us[market.long()]
+        o = torch.sort(t, stable=True).indices
+        o = o[torch.sort(sid[o], stable=True).indices]
+        bm = market[o].contiguous()
+        qpos, qlast, slast = torch.empty_like(p.qpos), torch.empty_like(p.qlast), torch.empty_like(p.slast)
+
+        def launch(p=p, bm=bm, qpos=qpos, qlast=qlast, slast=slast):
+            for _ in range(calls):
+                N.check(L.bce_walk_lag_queries(E, N.ptr(p.qentry), N.ptr(p.pairs.usid), N.ptr(p.pairs.emarket), E,
+                                               N.ptr(p.settle.start), S, N.ptr(bm), nb, N.ptr(p.forecast_time_us),
+                                               N.ptr(p.resolve_time_us), M, N.ptr(qpos), N.ptr(qlast), N.ptr(slast),
+                                               N.stream(dev)), "bce_walk_lag_queries")
+        launch()
+        torch.cuda.synchronize()
+        same_q = torch.equal(qpos, p.qpos) and torch.equal(qlast, p.qlast) and torch.equal(slast, p.slast)
+        launches.append((f"bce_walk_lag_queries alone, {label}", launch, same_q))
+    say(f"the launch alone reproduces the plans' queries: {all(x[2] for x in launches)}")
+    bins = batch.Plan.build_device(off)
+    table = Table(S, dev)
+    names = [""] * S
+
+    def whole(p, *mt):
+        def run():
+            for _ in range(calls):
+                table.reset()
+                batch.walk_forward(p, batch.ReliabilityTable(*table.live, names), *mt, offsets=off, prob=prob,
+                                   bins=bins, validate=False)
+        return run
+
+    variants = [(label, run) for label, run, _ in launches]
+    variants += [("walk_forward, ordinary plan", whole(plain, forecast)),
+                 ("walk_forward, lagged plan, resolve == forecast", whole(zero)),
+                 ("walk_forward, lagged plan, lag 0..72 h", whole(lagged))]
+    snaps = []
+    for label, run in variants[2:]:  # warm-up and the result check
+        run()
+        torch.cuda.synchronize()
+        snaps.append(table.snapshot())
+    same_table = same(snaps[0], snaps[1])
+    say(f"the ordinary walk and the lagged one with resolve == forecast leave identical tables: {same_table}")
+    N.check_faults(dev, "bench walk lag")
+    times = {label: [] for label, _ in variants}
+    for _ in range(max(args.reps, 3)):
+        for label, run in variants:
+            times[label].append(timed(run)[0] / calls)
+    for label, _ in variants:
+        say(f"(f) {label:<46} ms/call: {fmt(times[label])}   (min {min(times[label]) * 1e3:.3f})")
+    steps = 1 + int(np.ceil(np.log2(max(nb / max(plain.settle.n_touched, 1), 1) + 1)))
+    nbytes = E * (4 + 4 + 4 + 8 + 8 + 4) + E * steps * (4 + 8) + S * (16 + 4 + 8)
+    tq = min(times[launches[1][0]])
+    say(f"byte model of the launch: {nbytes / 1e6:.1f} MB at about {steps} bisection steps per query -> "
+        f"{100 * nbytes / tq / 8.0e12:.2f}% of 8 TB/s")
+    return same_plan and same_table and all(x[2] for x in launches)
+
+
 def run_slice(off_h, sid_h, prob_h, outcome_h, S, args, say):
     """(e): the first --slice-markets markets, the per-market loop against one walk_forward."""
     dev = torch.device("cuda", 0)
@@ -188,8 +286,11 @@ def main() -> int:
     ap.add_argument("--long-min", type=int, nargs="+", default=[256, 1024, 4096])
     ap.add_argument("--chunk-bits", type=int, nargs="+", default=[64, 256, 1024])
     ap.add_argument("--shapes", default="c3,uniform")
-    ap.add_argument("--out", default=os.path.join(ROOT, "measurements", "walk_forward.txt"))
+    ap.add_argument("--lag", action="store_true", help="(f): the walk with resolution lag, in place of (a)-(e)")
+    ap.add_argument("--out", default=None, help="default: measurements/walk_forward.txt (--lag: walk_lag.txt)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "measurements", "walk_lag.txt" if args.lag else "walk_forward.txt")
     N.require_gpu()  # a measurement without a GPU fails; there is nothing else to time
     lines = []
 
@@ -202,7 +303,13 @@ def main() -> int:
     off_h, sid_h, _, _ = make_c3_full(total=args.signals, S=args.sources)
     ok = True
     for shape in args.shapes.split(","):
-        if shape == "c3":
+        if args.lag and shape in ("c3", "uniform"):
+            src = sid_h
+            if shape == "uniform":
+                src = np.random.default_rng(71).integers(0, args.sources, len(sid_h)).astype(np.int32)
+            ok = run_lag("c3 (Zipf 1.1 sources)" if shape == "c3" else "uniform sources", off_h, src, args.sources,
+                         args, say) and ok
+        elif shape == "c3":
             ok = run_shape("c3 (Zipf 1.1 sources)", off_h, sid_h, args.sources, args, say)[0] and ok
         elif shape == "uniform":
             usid = np.random.default_rng(71).integers(0, args.sources, len(sid_h)).astype(np.int32)
