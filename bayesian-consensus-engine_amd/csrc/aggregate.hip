@@ -13,7 +13,8 @@
 // chunks of 1024 members are gathered (indices two chunks ahead, values one chunk ahead of
 // use), compacted into LDS in list order with ballots, and three lanes of wave 0 carry the
 // three ordered chains in 8-term batches; the median is an exact 8-pass
-// MSB radix select over order-preserving 64-bit keys (no sort, no extra memory).
+// MSB radix select over order-preserving 64-bit keys (no sort, no extra memory); a selected
+// zero is then looked up by list position, because sorted() is stable and 0.0 == -0.0.
 #include "bce_device.hpp"
 #include "bce_internal.hpp"
 #include "ordered_chain.hpp"
@@ -38,7 +39,9 @@ struct AggArgs {
 };
 
 // Order-preserving key of a double (total order; -0.0 is keyed as +0.0 because sorted()
-// treats them as equal).
+// treats them as equal -- which of a group's zeros is selected is settled by list position
+// after the passes, see kAggZeroKey in the kernel).
+constexpr uint64_t kAggZeroKey = 0x8000000000000000ull;
 __device__ __forceinline__ uint64_t f64_key(double x) {
   if (x == 0.0) x = 0.0;
   const uint64_t u = (uint64_t)__double_as_longlong(x);
@@ -229,7 +232,52 @@ __global__ __launch_bounds__(kAggT) __attribute__((amdgpu_waves_per_eu(kAggWpe, 
         }
         __syncthreads();
       }
-      if (t == 0) a.median[g] = (k > 0) ? key_f64(sPrefix) : __longlong_as_double(0x7FF8000000000000ll);
+      // Wave 0 alone writes the median (the other waves go on to the barrier below).  When the
+      // selected key is the zero key, the value is a zero, and the two zeros share that key.
+      // sorted() is stable, so its element k // 2 is the zero number sRank (what the passes left
+      // of the rank: k // 2 less the kept values below zero) of the group's kept zeros in list
+      // order.  One more pass over the values, 4 x 64 per step, finds it by ballot prefix counts,
+      // and that lane writes its own bits.  Wave-uniform, and run only for a zero median.
+      if (w == 0) {
+        const uint64_t sel = sPrefix;
+        if (k > 0 && sel == kAggZeroKey) {
+          const int64_t want = sRank;
+          const int64_t n = in_lds ? k : e - b;
+          int64_t seen = 0;
+          // the lane index (t in wave 0) made opaque here, so that no address of this branch is
+          // formed ahead of the group loop and held (spilled) across the chunk loop
+          int lz = t;
+          asm volatile("" : "+v"(lz));
+          for (int64_t j0 = 0; j0 < n && seen <= want; j0 += 4 * 64) {
+            double z[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int64_t j = j0 + r * 64 + lz;
+              z[r] = 1.0;
+              if (j < n) {
+                if (in_lds) {
+                  z[r] = sV[1][j];
+                } else {
+                  const int64_t m = a.members[b + j];
+                  if (m >= 0 && m < a.n_markets && a.has[m]) z[r] = a.cons[m];
+                }
+              }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const bool is0 = z[r] == 0.0;
+              const unsigned long long zm = ballot(is0);
+              // zeros in the lanes below this one (mbcnt: no lane mask held in registers)
+              const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(zm >> 32),
+                                                               __builtin_amdgcn_mbcnt_lo((unsigned)zm, 0u));
+              if (is0 && seen + below == want) a.median[g] = z[r];
+              seen += __popcll(zm);
+            }
+          }
+        } else if (t == 0) {
+          a.median[g] = (k > 0) ? key_f64(sel) : __longlong_as_double(0x7FF8000000000000ll);
+        }
+      }
     }
     __syncthreads();  // LDS state reused by the next group
   }

@@ -288,7 +288,8 @@ int bce_tiebreak_csr_long(const int64_t* offsets, int64_t n_markets, const int32
 
 /* ---- agreement statistics: CrossMarketAggregator.summarize_sources counts -----------
  * (market.py:279-304).  outcome[m]: -1 skip (unresolved), 0 false, 1 true.
- * correct[sid] / total[sid] are ACCUMULATED (zero them first); int32 atomics, exact. */
+ * correct[sid] / total[sid] are ACCUMULATED (zero them first); int32 atomics, exact.
+ * sid is not range-checked and must lie in [0, len(correct)). */
 int bce_agreement_stats(const int64_t* offsets, int64_t n_markets, const int32_t* sid,
                         const double* prob, const int8_t* outcome, int32_t* correct,
                         int32_t* total, void* stream);
@@ -301,7 +302,11 @@ int bce_agreement_stats(const int64_t* offsets, int64_t n_markets, const int32_t
  * (:369-375).  Per group (outputs nullable): wavg = weighted_average (:386-393), median
  * = sorted(consensus)[k // 2] (:394-397), majority (:398-401), mean_conf = the result's
  * confidence (:407), n_included = k.  k == 0 => the float outputs are NaN (the reference
- * returns consensus None).  Sums are left to right in list order: bit-exact. */
+ * returns consensus None).  Sums are left to right in list order: bit-exact.  A member index
+ * outside [0, n_markets) counts as a market without a consensus (skipped, nothing is read).  The
+ * median is the element sorted() would return -- sorted() is stable and compares 0.0 == -0.0, so
+ * a zero median keeps the sign of the zero at that list position.  The median of a group holding
+ * a NaN consensus is unspecified. */
 int bce_aggregate_groups(const int64_t* group_offsets, int64_t n_groups, const int64_t* members,
                          int64_t n_markets, const double* consensus, const double* confidence,
                          const uint8_t* has_consensus, double* wavg, double* median,

@@ -353,29 +353,39 @@ void orc_namespace_resolve(int64_t n, const double* const rel[3], const double* 
     }
 }
 
-static int cmp_f64(const void* a, const void* b) {
-    const double x = *(const double*)a, y = *(const double*)b;
-    return (x < y) ? -1 : (x > y) ? 1 : 0;
+/* sorted() is stable: by value (-0.0 == 0.0), equal values in list order.  The position is
+ * part of the key, so the result does not depend on qsort being stable. */
+typedef struct { double v; int64_t pos; } agg_val;
+static int cmp_agg_val(const void* a, const void* b) {
+    const agg_val* x = (const agg_val*)a;
+    const agg_val* y = (const agg_val*)b;
+    if (x->v < y->v) return -1;
+    if (x->v > y->v) return 1;
+    return (x->pos < y->pos) ? -1 : (x->pos > y->pos) ? 1 : 0;
 }
 
 /* market.py:340-408 (CrossMarketAggregator.aggregate_consensus) per member group:
- * k = members with a consensus; sums left to right in list order from 0.0. */
-void orc_aggregate_groups(const int64_t* goff, int64_t n_groups, const int64_t* members,
-                          const double* cons, const double* conf, const uint8_t* has,
-                          double* wavg, double* median, double* majority, double* mean_conf,
-                          int64_t* n_included) {
+ * k = members with a consensus; sums left to right in list order from 0.0.  A member outside
+ * [0, n_markets) is a market without a consensus.  median = sorted(cons)[k // 2], the element
+ * itself (a zero keeps its sign); with a NaN among the values it is unspecified. */
+void orc_aggregate_groups_n(const int64_t* goff, int64_t n_groups, const int64_t* members,
+                            int64_t n_markets, const double* cons, const double* conf,
+                            const uint8_t* has, double* wavg, double* median, double* majority,
+                            double* mean_conf, int64_t* n_included) {
     for (int64_t g = 0; g < n_groups; ++g) {
         double tconf = 0.0, tcons = 0.0, tprod = 0.0;
         int64_t k = 0, votes = 0;
-        double* vals = (double*)malloc(sizeof(double) * (size_t)(goff[g + 1] - goff[g] + 1));
+        agg_val* vals = (agg_val*)malloc(sizeof(agg_val) * (size_t)(goff[g + 1] - goff[g] + 1));
         for (int64_t i = goff[g]; i < goff[g + 1]; ++i) {
             const int64_t m = members[i];
-            if (!has[m]) continue;
+            if (m < 0 || m >= n_markets || !has[m]) continue;
             tconf = tconf + conf[m];
             tcons = tcons + cons[m];
             tprod = tprod + cons[m] * conf[m];
             votes += cons[m] >= 0.5;
-            vals[k++] = cons[m];
+            vals[k].v = cons[m];
+            vals[k].pos = k;
+            ++k;
         }
         n_included[g] = k;
         if (k == 0) {
@@ -384,9 +394,18 @@ void orc_aggregate_groups(const int64_t* goff, int64_t n_groups, const int64_t* 
             wavg[g] = (tconf == 0.0) ? tcons / (double)k : tprod / tconf;
             majority[g] = (double)votes / (double)k;
             mean_conf[g] = tconf / (double)k;
-            qsort(vals, (size_t)k, sizeof(double), cmp_f64);
-            median[g] = vals[k / 2];
+            qsort(vals, (size_t)k, sizeof(agg_val), cmp_agg_val);
+            median[g] = vals[k / 2].v;
         }
         free(vals);
     }
+}
+
+/* The entry without n_markets (callers whose members all index a market): no upper bound. */
+void orc_aggregate_groups(const int64_t* goff, int64_t n_groups, const int64_t* members,
+                          const double* cons, const double* conf, const uint8_t* has,
+                          double* wavg, double* median, double* majority, double* mean_conf,
+                          int64_t* n_included) {
+    orc_aggregate_groups_n(goff, n_groups, members, INT64_MAX, cons, conf, has, wavg, median, majority,
+                           mean_conf, n_included);
 }

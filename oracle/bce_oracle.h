@@ -89,7 +89,14 @@ void orc_namespace_resolve(int64_t n, const double* const rel[3], const double* 
                            double default_rel, double default_conf, double* rel_out,
                            double* conf_out, uint8_t* scope_out);
 
-/* CrossMarketAggregator.aggregate_consensus (market.py:340-408) per member group. */
+/* CrossMarketAggregator.aggregate_consensus (market.py:340-408) per member group.  A member
+ * outside [0, n_markets) is skipped; the median is the element sorted() returns (stable: equal
+ * values, the two zeros included, in list order). */
+void orc_aggregate_groups_n(const int64_t* goff, int64_t n_groups, const int64_t* members,
+                            int64_t n_markets, const double* cons, const double* conf,
+                            const uint8_t* has, double* wavg, double* median, double* majority,
+                            double* mean_conf, int64_t* n_included);
+/* The same for members that all index a market (no n_markets, no upper bound). */
 void orc_aggregate_groups(const int64_t* goff, int64_t n_groups, const int64_t* members,
                           const double* cons, const double* conf, const uint8_t* has,
                           double* wavg, double* median, double* majority, double* mean_conf,

@@ -172,6 +172,7 @@ def namespace_resolve(scopes, apply_decay, now_us, half_life=30.0, min_rel=0.10,
 
 
 def aggregate_groups(goff, members, cons, conf, has):
+    """n_markets = len(cons): a member outside [0, n_markets) is skipped."""
     goff = np.ascontiguousarray(goff, np.int64)
     members = np.ascontiguousarray(members, np.int64)
     cons = np.ascontiguousarray(cons, np.float64)
@@ -180,7 +181,8 @@ def aggregate_groups(goff, members, cons, conf, has):
     G = len(goff) - 1
     out = dict(wavg=np.zeros(G), median=np.zeros(G), majority=np.zeros(G), mean_conf=np.zeros(G),
                n_included=np.zeros(G, np.int64))
-    lib().orc_aggregate_groups(_p(goff), C.c_int64(G), _p(members), _p(cons), _p(conf), _p(has),
-                               _p(out["wavg"]), _p(out["median"]), _p(out["majority"]), _p(out["mean_conf"]),
-                               _p(out["n_included"]))
+    assert len(conf) == len(cons) and len(has) == len(cons)
+    lib().orc_aggregate_groups_n(_p(goff), C.c_int64(G), _p(members), C.c_int64(len(cons)), _p(cons), _p(conf),
+                                 _p(has), _p(out["wavg"]), _p(out["median"]), _p(out["majority"]),
+                                 _p(out["mean_conf"]), _p(out["n_included"]))
     return out

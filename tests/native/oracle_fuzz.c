@@ -94,6 +94,8 @@ static void one_batch(int it) {
   double *wa = xcalloc(G, 8), *md = xcalloc(G, 8), *mj = xcalloc(G, 8), *mc = xcalloc(G, 8);
   int64_t* inc = xcalloc(G, 8);
   orc_aggregate_groups(goff, G, mem, cons, cf, has, wa, md, mj, mc, inc);
+  for (int64_t i = 0; i < goff[G]; i += 7) mem[i] = (i & 1) ? M : -1; /* skipped, never read */
+  orc_aggregate_groups_n(goff, G, mem, M, cons, cf, has, wa, md, mj, mc, inc);
   /* re-estimation on a small dense matrix */
   const int64_t A = 1 + (int64_t)(rnd() % 20), MM = 1 + (int64_t)(rnd() % 50);
   double *P = xcalloc(A * MM, 8), *wr = xcalloc(A, 8), *co2 = xcalloc(2 * MM, 8);

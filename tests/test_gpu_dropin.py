@@ -392,6 +392,65 @@ def test_reestimate_votes_match_two_pass(A, M):
         assert np.array_equal(bits.transpose(0, 2, 1).reshape(K * 64, A), exp)
 
 
+@pytest.mark.parametrize("A", [3, 17])
+@pytest.mark.parametrize("M", [16 * 1024, 16 * 1024 + 1, 19 * 1024 - 5])
+def test_reestimate_votes_column_ranges_vs_numpy(A, M):
+    """16, 17 and 19 workgroups of 1024 columns: from 8 up the votes kernels deal the workgroups to
+    column ranges (per = 2 here; the last 0, 1 and 3 workgroups keep their own).  Both entries
+    against numpy in agent order -- ws = ws + (0.0 + P[a]) * w[a], total = total + w[a], each step
+    one IEEE operation over all columns -- with every output pre-filled, so that a column range
+    computed twice or never shows.  A = 3 is the tail loop only, A = 17 one 16-row batch and a tail."""
+    import torch
+    from bayesian_engine import _native as N
+    rng = np.random.default_rng(A * 100_003 + M)
+    P = rng.beta(2, 2, size=(A, M))
+    P[:, rng.random(M) < 0.05] = 0.5
+    w = rng.uniform(0.01, 0.99, A)
+    ws, total = np.zeros(M), 0.0
+    for a in range(A):
+        ws = ws + (0.0 + P[a]) * w[a]
+        total = total + w[a]
+    cons = ws / total
+    K = (M + 63) // 64
+
+    def pack(bits):  # [M] bool -> K words, bit m % 64 of word m // 64
+        pad = np.zeros(K * 64, np.uint8)
+        pad[:M] = bits
+        return np.packbits(pad, bitorder="little").view(np.uint64)
+
+    votes_exp = np.stack([pack(P[a] >= 0.5) for a in range(A)], axis=1)  # [K, A]
+    agree_exp = ((P >= 0.5) == (cons >= 0.5)[None, :]).sum(axis=1)
+    Pt, wt = torch.from_numpy(P).cuda(), torch.from_numpy(w).cuda()
+    L = N.lib()
+    st = N.stream(Pt.device)
+    nb = int(L.bce_reestimate_mfma_scratch_bytes(M))
+    scratch = torch.empty((nb + 7) // 8, dtype=torch.int64, device="cuda")
+    for fn in ("bce_reestimate_consensus_votes", "bce_reestimate_consensus_votes_mfma"):
+        c = torch.full((M,), float("nan"), dtype=torch.float64, device="cuda")
+        nu = torch.full((M,), 255, dtype=torch.uint8, device="cuda")
+        votes = torch.full((K, A), -1, dtype=torch.int64, device="cuda")
+        words = torch.full((2, K), -1, dtype=torch.int64, device="cuda")
+        g = torch.zeros(A + 1, dtype=torch.int64, device="cuda")
+        extra = (N.ptr(scratch), scratch.numel() * 8) if fn.endswith("mfma") else ()
+        N.check(getattr(L, fn)(N.ptr(Pt), A, M, M, N.ptr(wt), N.ptr(c), N.ptr(nu), N.ptr(votes), N.ptr(words[0]),
+                               N.ptr(words[1]), *extra, st), fn)
+        N.check(L.bce_reestimate_agreement_votes(N.ptr(votes), A, M, N.ptr(words[0]), N.ptr(words[1]),
+                                                 N.ptr(g[:A]), N.ptr(g[A:]), st))
+        torch.cuda.synchronize()
+        got = c.cpu().numpy()
+        if fn.endswith("mfma"):
+            assert not np.isnan(got).any(), fn
+            assert np.abs(got - cons).max() <= 4 * (A + 2) * 2.0 ** -53, fn
+        else:
+            assert np.array_equal(got, cons), fn
+        assert not nu.cpu().numpy().any(), fn
+        assert np.array_equal(votes.cpu().numpy().view(np.uint64), votes_exp), fn
+        wd = words.cpu().numpy().view(np.uint64)
+        assert np.array_equal(wd[1], pack(np.ones(M, bool))), fn  # ok_words: every market resolved
+        assert np.array_equal(wd[0], pack(cons >= 0.5)), fn       # cvote_words: of the exact consensus
+        assert np.array_equal(g.cpu().numpy(), np.append(agree_exp, M)), fn
+
+
 def test_c4_replay_slice():
     """Config-4 replay through the fused replay_step kernel vs the reference trace."""
     import torch

@@ -169,6 +169,44 @@ def test_namespace_kernel_vs_oracle(S, present, apply_decay):
 
 
 @pytest.mark.gpu
+def test_namespace_kernel_past_one_grid():
+    """S = 8192 * 256 + 65: the grid is capped at 8192 workgroups of 256 sources, so the first 65
+    workgroups take a second stride (and its present-bit words); three scopes, decay on."""
+    import torch
+
+    from bayesian_engine import batch
+    from bayesian_engine.timeutil import NO_TIMESTAMP
+
+    S = 8192 * 256 + 65
+    rng = np.random.default_rng(8192)
+    now_us = 1_772_366_400_000_000
+    scopes_np, scopes_dev = [], []
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(_dev())  # noqa: E731
+    for q in range(3):
+        rel = np.where(rng.random(S) < 0.3, rng.choice([0.0, 0.05, 1.0, 1.3, 0.5], S), rng.random(S))
+        conf = rng.random(S)
+        t = now_us - rng.integers(-5 * 86_400_000_000, 400 * 86_400_000_000, S)
+        t[rng.random(S) < 0.1] = NO_TIMESTAMP
+        has = (rng.random(S) < 0.4).astype(np.uint8)
+        scopes_np.append((rel, conf, t, has))
+        scopes_dev.append(batch.ScopeTable(T(rel), T(conf), T(t), T(has)))
+    rel_o, conf_o, code_o = orc.namespace_resolve(scopes_np, True, now_us)
+    assert set(np.unique(code_o[-65:])) == {0, 1, 2, 3}  # the second stride sees every scope
+    for mark_cold in (False, True):
+        table, code = batch.namespace_resolve(scopes_dev, now_us, apply_decay=True, mark_cold=mark_cold)
+        torch.cuda.synchronize()
+        rc = table.relconf[:S].cpu().numpy()
+        assert np.array_equal(code.cpu().numpy(), code_o)
+        assert np.array_equal(rc[:, 1], conf_o)
+        assert np.array_equal(rc[:, 0], rel_o)
+        words = table.bits.cpu().numpy().view(np.uint8)
+        got = np.unpackbits(words, bitorder="little")
+        exp = (code_o != 3).astype(np.uint8) if mark_cold else np.ones(S, np.uint8)
+        assert np.array_equal(got[:S], exp)
+        assert not got[S:].any()  # the pad bits of the last word stay clear
+
+
+@pytest.mark.gpu
 def test_namespace_store_golden(tmp_path):
     """The drop-in store: per-row get_reliability (frozen clock) and the one-launch bulk
     path both reproduce the reference's records."""
@@ -276,8 +314,9 @@ def test_aggregate_store_golden():
 @pytest.mark.parametrize("G,maxlen", [(1, 0), (7, 1), (300, 40), (50, 3000), (3, 200_000), (5000, 40), (3000, 2500),
                                       (9000, 3)])
 def test_aggregate_kernel_vs_oracle(G, maxlen):
-    """Many more groups than workgroups (each workgroup pipelines its groups as one chunk
-    stream, across group boundaries), empty groups, multi-chunk groups."""
+    """One workgroup per group (measurements/agg_pipeline_r02.txt), each pipelining its own
+    chunks of 1024 members: many more groups than the chip holds at once, empty groups,
+    one-chunk groups (median from LDS) and multi-chunk groups (median re-reads the members)."""
     import torch
 
     from bayesian_engine import batch
