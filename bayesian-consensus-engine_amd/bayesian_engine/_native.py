@@ -108,6 +108,8 @@ _SIGS = {
                                     _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "bce_walk_scope_read": (C.c_int, [_i64, _vp, _vp, _vp, _i64, _i32] + [_vp] * 6 + [_i64] + [_vp] * 7 + [_i64] +
                             [_vp] * 6 + [_f64, _f64, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "bce_walk_scope_read_lag": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _i64, _i32] + [_vp] * 6 + [_i64] + [_vp] * 7 +
+                                [_i64] + [_vp] * 6 + [_f64, _f64, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "bce_namespace_resolve": (C.c_int, [_i64] + [_vp] * 12 + [_i32, _i64, _f64, _f64, _f64, _f64, _i32,
                                                                _vp, _vp, _vp, _vp]),
     "bce_pair_resolve": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _i64] + [_vp] * 6 + [_i64, _i32] + [_vp] * 8 +

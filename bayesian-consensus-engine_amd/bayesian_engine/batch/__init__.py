@@ -29,11 +29,12 @@ from .pairs import (_PAIR_MODES, DomainPlan, PairConsensusResult, PairPlan, Pair
                     _check_queries, _cut, _dense_scope, _entry_outputs, _pair_merge, _pair_merge_index,
                     _pair_pointers, consensus_pairs, pair_resolve, scope_resolve, settle_domains, settle_pairs)
 from .walk import (WALK_CHUNK_BITS, WALK_LONG_MIN, WalkPlan, WalkQueries, WalkResult, WalkScopePlan, WalkScopeResult,
-                   _chain_queries, _check_lag_times, _entry_signals, _global_outcome, _walk_buffers, _walk_queries,
-                   _walk_read, _walk_scope_read, _walk_settle_trace, _walk_times, walk_forward, walk_forward_scoped,
-                   walk_scope_trace, walk_trace)
+                   _chain_queries, _check_lag_times, _entry_signals, _global_outcome, _lag_family, _resolve_rank,
+                   _walk_buffers, _walk_queries, _walk_read, _walk_scope_launch, _walk_scope_read, _walk_scope_traces,
+                   _walk_settle_trace, _walk_times, walk_forward, walk_forward_scoped, walk_scope_trace, walk_trace)
 from .glob import (_GLOB_ANY, _GLOB_CLS, _GLOB_LIT, _GLOB_NEGATE, _GLOB_STAR, GLOB_MAX_OPS, GLOB_MAX_RANGES, GlobSet,
                    NameTable, _glob_bracket, _glob_compile_one, _glob_host_row, _GlobDeclined, _np_or_dummy, glob_any,
                    glob_count, glob_mask, glob_match, glob_match_host, glob_members)
 from .score import (SCORE_COUNTS, SCORE_LANES, SCORE_MAX_BINS, SCORE_SEG, SCORE_SUMS, ScorePlan, ScoreResult,
-                    _nan_div, _score_segments, score, score_markets, score_sources, walk_sweep)
+                    _nan_div, _score_segments, score, score_markets, score_sources, walk_sweep,
+                    walk_sweep_scoped)

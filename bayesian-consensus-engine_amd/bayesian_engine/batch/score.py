@@ -8,7 +8,8 @@ from .. import _native as N
 from .tables import ReliabilityTable, SourceTable, _check_csr, _entry_buffers
 from .consensus import Plan, _alloc, consensus
 from .pairs import _bins_as_plan
-from .walk import WalkPlan, _walk_read, _walk_settle_trace
+from .walk import (WalkPlan, WalkScopePlan, _walk_read, _walk_scope_launch, _walk_scope_traces,
+                   _walk_settle_trace)
 
 SCORE_SEG = N.SCORE_SEG          # items of a segment (include/bce.h BCE_SCORE_SEG)
 SCORE_LANES = N.SCORE_LANES      # lane partials of a segment
@@ -278,6 +279,52 @@ def score_sources(plan: ScorePlan, prob: torch.Tensor, outcome: torch.Tensor,
     return score(plan, prob.to(torch.float64), outcome, valid=valid, base=consensus, **kw)
 
 
+def _sweep_grid(half_life_days: Sequence[float], min_rel: Sequence[float], what: str):
+    """The grid of a sweep as two lists of floats; an empty axis is a ``ValueError``."""
+    hl, mr = [float(x) for x in half_life_days], [float(x) for x in min_rel]
+    if not hl or not mr:
+        raise ValueError(f"{what} needs at least one half_life_days and one min_rel")
+    return hl, mr
+
+
+def _sweep(pairs, outcome: torch.Tensor, read, wtable: SourceTable, offsets: torch.Tensor, prob: torch.Tensor, hl, mr,
+           score_plan: Optional[ScorePlan], keep_consensus: bool, mode: str, n_bins: int, eps: float,
+           consensus_kwargs: dict):
+    """The grid loop of :func:`walk_sweep` and :func:`walk_sweep_scoped`: for every point,
+    ``read(half_life_days, min_rel)`` fills ``wtable`` (the consensus table over the entries of
+    ``pairs``), then :func:`consensus` and :func:`score` against ``outcome``.  The length-bin
+    plan, the consensus outputs and the scoring scratch are allocated once."""
+    M, E = pairs.n_markets, pairs.n_entries
+    dev = wtable.relconf.device
+    if score_plan is None:
+        score_plan = ScorePlan.whole(M, device=dev)
+    prob = prob.to(torch.float64)
+    kw = _bins_as_plan(consensus_kwargs)
+    unique = kw.pop("unique_outputs", False)
+    validate = kw.pop("validate", False)
+    if kw.get("plan") is None and kw.get("max_len") is None:
+        kw["plan"] = Plan.build_device(offsets)  # the length bins once, not once per grid point
+    out = _alloc(M, pairs.esid.numel(), dev, unique, validate)
+    L = N.require_gpu()
+    sb = int(L.bce_score_scratch_bytes(score_plan.n_segments, int(n_bins))) if 1 <= int(n_bins) <= SCORE_MAX_BINS else 8
+    scratch = torch.empty(max(sb // 8, 1), dtype=torch.int64, device=dev)
+    empty = offsets[1:] == offsets[:-1]
+    parts, cons, nulls = [], [], []
+    for h in hl:
+        for m in mr:
+            read(h, m)
+            res = consensus(offsets, pairs.esid, prob, wtable, mode=mode, unique_outputs=unique, validate=validate,
+                            out=out, **kw)
+            null = (res.total_weight == 0) | empty
+            parts.append(score(score_plan, res.consensus, outcome, valid=~null, n_bins=n_bins, eps=eps,
+                               scratch=scratch))
+            if keep_consensus:
+                cons.append(res.consensus.clone())
+                nulls.append(null)
+    scores = ScoreResult.stack(parts)
+    return scores, ((torch.stack(cons), torch.stack(nulls)) if keep_consensus else None)
+
+
 def walk_sweep(plan: WalkPlan, table: "ReliabilityTable", market_time_us: Optional[torch.Tensor] = None, *,
                offsets: torch.Tensor, prob: torch.Tensor, half_life_days: Sequence[float], min_rel: Sequence[float],
                score_plan: Optional[ScorePlan] = None, keep_consensus: bool = False, all_present: bool = True,
@@ -295,44 +342,56 @@ def walk_sweep(plan: WalkPlan, table: "ReliabilityTable", market_time_us: Option
     ``[len(half_life_days) * len(min_rel), G, ...]`` over ``score_plan`` (default: one group of all
     markets) and, with ``keep_consensus``, the fp64 ``[K, M]`` consensus and bool ``[K, M]``
     null mask of every point (else None)."""
-    sp, pp = plan.settle, plan.pairs
-    hl, mr = [float(x) for x in half_life_days], [float(x) for x in min_rel]
-    if not hl or not mr:
-        raise ValueError("walk_sweep needs at least one half_life_days and one min_rel")
+    pp = plan.pairs
+    hl, mr = _sweep_grid(half_life_days, min_rel, "walk_sweep")
     if plan.outcome is None:
         raise ValueError("walk_sweep needs a WalkPlan from WalkPlan.build (it keeps the outcomes)")
     if offsets.numel() - 1 != pp.n_markets or prob.numel() != pp.esid.numel():
         raise ValueError("offsets / prob are not the batch the plan was built from")
-    M, E = pp.n_markets, pp.n_entries
+    E = pp.n_entries
     dev = table.rel.device
-    if score_plan is None:
-        score_plan = ScorePlan.whole(M, device=dev)
     trace, _, _ = _entry_buffers(E, dev)
     relconf, bits, exists = _entry_buffers(E, dev)
     _walk_settle_trace(plan, table, market_time_us, trace, long_min, chunk_bits)
-    prob = prob.to(torch.float64)
-    kw = _bins_as_plan(consensus_kwargs)
-    unique = kw.pop("unique_outputs", False)
-    validate = kw.pop("validate", False)
-    if kw.get("plan") is None and kw.get("max_len") is None:
-        kw["plan"] = Plan.build_device(offsets)  # the length bins once, not once per grid point
-    out = _alloc(M, pp.esid.numel(), dev, unique, validate)
-    L = N.require_gpu()
-    sb = int(L.bce_score_scratch_bytes(score_plan.n_segments, int(n_bins))) if 1 <= int(n_bins) <= SCORE_MAX_BINS else 8
-    scratch = torch.empty(max(sb // 8, 1), dtype=torch.int64, device=dev)
-    wtable = SourceTable(relconf, bits, range(E))
-    empty = offsets[1:] == offsets[:-1]
-    parts, cons, nulls = [], [], []
-    for h in hl:
-        for m in mr:
-            _walk_read(plan, table, market_time_us, trace, relconf, bits, exists, all_present, h, m)
-            res = consensus(offsets, pp.esid, prob, wtable, mode=mode, unique_outputs=unique, validate=validate,
-                            out=out, **kw)
-            null = (res.total_weight == 0) | empty
-            parts.append(score(score_plan, res.consensus, plan.outcome, valid=~null, n_bins=n_bins, eps=eps,
-                               scratch=scratch))
-            if keep_consensus:
-                cons.append(res.consensus.clone())
-                nulls.append(null)
-    scores = ScoreResult.stack(parts)
-    return scores, ((torch.stack(cons), torch.stack(nulls)) if keep_consensus else None)
+
+    def read(h, m):
+        _walk_read(plan, table, market_time_us, trace, relconf, bits, exists, all_present, h, m)
+
+    return _sweep(pp, plan.outcome, read, SourceTable(relconf, bits, range(E)), offsets, prob, hl, mr, score_plan,
+                  keep_consensus, mode, n_bins, eps, consensus_kwargs)
+
+
+def walk_sweep_scoped(plan: WalkScopePlan, domains: "PairTable", global_table: Optional["ReliabilityTable"],
+                      market_time_us: Optional[torch.Tensor] = None, *, offsets: torch.Tensor, prob: torch.Tensor,
+                      half_life_days: Sequence[float], min_rel: Sequence[float], pairs: Optional["PairTable"] = None,
+                      global_has: Optional[torch.Tensor] = None, score_plan: Optional[ScorePlan] = None,
+                      keep_consensus: bool = False, mark_cold: bool = False, mode: str = "exact",
+                      long_min: Optional[int] = None, chunk_bits: Optional[int] = None, n_bins: int = 10,
+                      eps: float = 1e-15, **consensus_kwargs):
+    """:func:`walk_sweep` over the namespaced walk: :func:`walk_forward_scoped` (``commit=False``),
+    ordinary or lagged, for every point of a grid of decay parameters, scored against the plan's
+    outcomes.  ``update_reliability`` starts from the undecayed row in every scope
+    (reliability_abstraction.py:211-229), so neither chain family depends on ``half_life_days`` /
+    ``min_rel``: each is traced ONCE into a buffer of its own, and every grid point runs
+    bce_walk_scope_read from the two traces into a THIRD buffer (the single walk lets the read
+    overwrite the global trace in place; here the traces must outlive the read), then
+    :func:`consensus` and :func:`score`.  No input is written.  The arguments are those of
+    :func:`walk_forward_scoped` and :func:`walk_sweep`; returns what :func:`walk_sweep` returns."""
+    pp = plan.pairs
+    hl, mr = _sweep_grid(half_life_days, min_rel, "walk_sweep_scoped")
+    if plan.outcome is None:
+        raise ValueError("walk_sweep_scoped needs a WalkScopePlan from WalkScopePlan.build (it keeps the outcomes)")
+    if offsets.numel() - 1 != pp.n_markets or prob.numel() != pp.esid.numel():
+        raise ValueError("offsets / prob are not the batch the plan was built from")
+    E = pp.n_entries
+    dev = pp.esid.device
+    gtrace, _, _ = _entry_buffers(E, dev)
+    relconf, bits, scope = _entry_buffers(E, dev)
+    tr = _walk_scope_traces(plan, domains, global_table, market_time_us, pairs, global_has, long_min, chunk_bits,
+                            gtrace)
+
+    def read(h, m):
+        _walk_scope_launch(plan, tr, global_table, market_time_us, pairs, mark_cold, h, m, relconf, bits, scope)
+
+    return _sweep(pp, plan.outcome, read, SourceTable(relconf, bits, range(E)), offsets, prob, hl, mr, score_plan,
+                  keep_consensus, mode, n_bins, eps, consensus_kwargs)

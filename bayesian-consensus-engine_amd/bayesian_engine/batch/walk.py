@@ -184,39 +184,70 @@ class WalkPlan:
         :meth:`build`'s, array for array."""
         M, _, S, _, _ = _check_csr(offsets, sid, n_sources, outcome=outcome, values=False)
         _check_lag_times(forecast_time_us, resolve_time_us, outcome, M)
-        dev = offsets.device
-        i64 = dict(dtype=torch.int64, device=dev)
         clamped = sid.to(torch.int32).clamp(0, S - 1)
         n_clamped = int((clamped != sid).sum())
         pairs = PairPlan.build(offsets, clamped, prob, S)  # checks offsets / prob
         forecast = forecast_time_us.contiguous()
         resolve = resolve_time_us.contiguous()
-        # the rank of every resolved market by (resolve time, market); the others behind them
-        key = torch.where(outcome >= 0, resolve, torch.full_like(resolve, torch.iinfo(torch.int64).max))
-        rank = torch.empty(M, **i64)
-        rank[torch.sort(key, stable=True).indices] = torch.arange(M, **i64)
-        L = N.require_gpu()
-        splan, market, perm = SettlePlan._compile(offsets, sid, prob, outcome, n_sources, check, rank)
-        bit_market = market[perm].contiguous()
-        E = pairs.n_entries
-        usid = pairs.usid[:E].to(torch.int64)
-        qentry = torch.sort(usid, stable=True).indices.to(torch.int32).contiguous()  # (source, market) order
-        qstart = torch.zeros(S + 1, **i64)
-        qstart[1:] = torch.cumsum(torch.bincount(usid, minlength=S), 0)
-        qpos = torch.empty(E, **i64)
-        qlast = torch.full((E,), -1, dtype=torch.int32, device=dev)
-        slast = torch.empty(S, **i64)
-        ent = lambda t: N.ptr(t if E else None)  # noqa: E731
-        N.check(L.bce_walk_lag_queries(E, ent(qentry), ent(pairs.usid), ent(pairs.emarket), E, N.ptr(splan.start), S,
-                                       N.ptr(bit_market if splan.n_bits else None), splan.n_bits,
-                                       N.ptr(forecast if M else None), N.ptr(resolve if M else None), M, ent(qpos),
-                                       ent(qlast), N.ptr(slast), N.stream(dev)), "bce_walk_lag_queries")
+        N.require_gpu()
+        splan, q = _lag_family(offsets, sid, prob, outcome, n_sources, check, _resolve_rank(outcome, resolve), pairs,
+                               pairs.usid, forecast, resolve)
         if check:
-            N.check_faults(dev, "walk lag queries")
+            N.check_faults(offsets.device, "walk lag queries")
             if n_clamped:  # in an unresolved market: the settlement compile does not see it
                 raise N.BCEError(f"walk plan: {n_clamped} sid outside [0, {int(n_sources)})")
-        return cls(splan, pairs, qstart, qpos, qentry, qlast, slast, n_clamped, outcome.contiguous(), forecast,
-                   resolve)
+        return cls(splan, pairs, q.qstart, q.qpos, q.qentry, q.qlast, q.slast, n_clamped, outcome.contiguous(),
+                   forecast, resolve)
+
+
+def _resolve_rank(outcome: torch.Tensor, resolve: torch.Tensor) -> torch.Tensor:
+    """int64[M]: the rank of every resolved market by (resolve time, market); the others behind
+    them (one stable sort over M, any device)."""
+    M = outcome.numel()
+    i64 = dict(dtype=torch.int64, device=outcome.device)
+    key = torch.where(outcome >= 0, resolve, torch.full_like(resolve, torch.iinfo(torch.int64).max))
+    rank = torch.empty(M, **i64)
+    rank[torch.sort(key, stable=True).indices] = torch.arange(M, **i64)
+    return rank
+
+
+def _lag_family(offsets: torch.Tensor, chain_sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
+                n_chains: int, check: bool, rank: torch.Tensor, pairs: PairPlan, chain: torch.Tensor,
+                forecast: torch.Tensor, resolve: torch.Tensor, partial: bool = False):
+    """One chain family of a lagged plan: ``(SettlePlan, WalkQueries)``.  The chains are those of
+    ``(offsets, chain_sid, prob, outcome)`` over ``n_chains`` chain ids, compiled in (``rank``,
+    position) order; ``chain`` int32[>= E] is the chain every entry of ``pairs`` reads.  The
+    queries are the entries in (chain, market) order -- with ``partial``, only those with ``chain
+    >= 0``; the ``qlast`` of the others stays -1 -- and one launch of bce_walk_lag_queries bisects
+    every query's visible prefix and reads every chain's last market.  The fault word is left to
+    the caller, who has passed ``_native.require_gpu()``."""
+    L = N.lib()
+    splan, market, perm = SettlePlan._compile(offsets, chain_sid, prob, outcome, n_chains, check, rank)
+    bit_market = market[perm].contiguous()
+    E, M, C = pairs.n_entries, pairs.n_markets, splan.n_sources
+    dev = offsets.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    key = chain[:E].to(torch.int64)
+    if partial:
+        sel = torch.nonzero(key >= 0).flatten()
+        key = key[sel]
+    qentry = torch.sort(key, stable=True).indices  # entries ascend by market: (chain, market) order
+    if partial:
+        qentry = sel[qentry]
+    qentry = qentry.to(torch.int32).contiguous()
+    Q = qentry.numel()
+    qstart = torch.zeros(C + 1, **i64)
+    qstart[1:] = torch.cumsum(torch.bincount(key, minlength=C), 0)
+    qpos = torch.empty(Q, **i64)
+    qlast = torch.full((E,), -1, dtype=torch.int32, device=dev)
+    slast = torch.empty(C, **i64)
+    ent = lambda t: N.ptr(t if E else None)  # noqa: E731
+    qry = lambda t: N.ptr(t if Q else None)  # noqa: E731
+    N.check(L.bce_walk_lag_queries(Q, qry(qentry), ent(chain), ent(pairs.emarket), E, N.ptr(splan.start), C,
+                                   N.ptr(bit_market if splan.n_bits else None), splan.n_bits,
+                                   N.ptr(forecast if M else None), N.ptr(resolve if M else None), M, qry(qpos),
+                                   ent(qlast), N.ptr(slast), N.stream(dev)), "bce_walk_lag_queries")
+    return splan, WalkQueries(qstart, qpos, qentry, qlast, slast)
 
 
 def _check_lag_times(forecast_time_us: torch.Tensor, resolve_time_us: torch.Tensor, outcome: torch.Tensor,
@@ -236,9 +267,10 @@ def _check_lag_times(forecast_time_us: torch.Tensor, resolve_time_us: torch.Tens
         raise ValueError(f"market {at} resolves before it is forecast")
 
 
-def _walk_times(plan: WalkPlan, market_time_us: Optional[torch.Tensor]):
+def _walk_times(plan, market_time_us: Optional[torch.Tensor]):
     """``(stamp, now)``: the time a market's updates are stamped with and the time it is read at
-    -- the plan's resolve and forecast times, or ``market_time_us`` twice."""
+    -- the plan's resolve and forecast times, or ``market_time_us`` twice.  ``plan``: a
+    :class:`WalkPlan` or a :class:`WalkScopePlan`."""
     if plan.lagged:
         if market_time_us is not None:
             raise ValueError("a lagged plan carries its own times: market_time_us must be None")
@@ -389,7 +421,12 @@ class WalkScopePlan:
     compiles it) and of the global chains (over the S sources: the resolved markets without a
     domain, or every resolved market with ``update_global``); ``dq`` / ``gq``: the
     :class:`WalkQueries` of either family -- every entry is a query of its global chain, and of
-    its domain chain where ``dentry >= 0``.  ``n_clamped``: sids outside ``[0, n_sources)``."""
+    its domain chain where ``dentry >= 0``.  ``n_clamped``: sids outside ``[0, n_sources)``.
+
+    A plan from :meth:`build_lagged` (``lagged``) carries a forecast and a resolve time per market
+    (DESIGN §4.22): the chains of both families are in (resolve time, market, position) order, the
+    queries count the bits resolved before the entry's forecast, and the walk takes its times from
+    the plan."""
 
     pairs: PairPlan
     dplan: "DomainPlan"
@@ -400,14 +437,19 @@ class WalkScopePlan:
     gq: WalkQueries
     update_global: bool
     n_clamped: int
+    outcome: Optional[torch.Tensor] = None  # int8[M], as given to build (scoring reads it)
+    forecast_time_us: Optional[torch.Tensor] = None  # int64[M], build_lagged only
+    resolve_time_us: Optional[torch.Tensor] = None   # int64[M], read where outcome >= 0
+
+    @property
+    def lagged(self) -> bool:
+        return self.forecast_time_us is not None
 
     @classmethod
-    def order(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
-              market_domain: torch.Tensor, n_sources: int, n_domains: int, update_global: bool = False):
-        """The integer half of :meth:`build` (torch only, CPU tensors included): ``(pairs, dplan,
-        dentry, dq, gq, n_clamped)``.  Argument errors as :meth:`WalkPlan.order` and
-        :meth:`DomainPlan.build`."""
-        S = _check_csr(offsets, sid, n_sources, outcome=outcome, values=False)[2]
+    def _entries(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, market_domain: torch.Tensor,
+                 S: int, n_domains: int):
+        """``(pairs, dplan, dentry int64[E], n_clamped)``: the entry list, the (domain, source)
+        chains and the chain of every entry (torch only, any device)."""
         clamped = sid.to(torch.int32).clamp(0, S - 1)
         n_clamped = int((clamped != sid).sum())
         dplan = DomainPlan.build(offsets, clamped, market_domain, S, n_domains)  # checks market_domain / offsets
@@ -419,7 +461,19 @@ class WalkScopePlan:
         # the (domain, source) keys of the DomainPlan ascend: the chain of an entry by search
         fkey = dplan.emarket[:F].to(torch.int64) * S + dplan.usid[:F].to(torch.int64)
         at = torch.searchsorted(fkey, edom.clamp(min=0) * S + usid) if F else torch.zeros_like(usid)
-        dentry = torch.where(edom >= 0, at, torch.full_like(at, -1))
+        return pairs, dplan, torch.where(edom >= 0, at, torch.full_like(at, -1)), n_clamped
+
+    @classmethod
+    def order(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
+              market_domain: torch.Tensor, n_sources: int, n_domains: int, update_global: bool = False):
+        """The integer half of :meth:`build` (torch only, CPU tensors included): ``(pairs, dplan,
+        dentry, dq, gq, n_clamped)``.  Argument errors as :meth:`WalkPlan.order` and
+        :meth:`DomainPlan.build`."""
+        S = _check_csr(offsets, sid, n_sources, outcome=outcome, values=False)[2]
+        pairs, dplan, dentry, n_clamped = cls._entries(offsets, sid, prob, market_domain, S, n_domains)
+        E, F = pairs.n_entries, dplan.n_entries
+        usid = pairs.usid[:E].to(torch.int64)
+        emarket = pairs.emarket[:E].to(torch.int64)
         signals = _entry_signals(pairs)
         dq = WalkQueries(*_chain_queries(dentry, signals * (outcome[emarket] >= 0), emarket, max(F, 1),
                                          partial=True))
@@ -445,7 +499,45 @@ class WalkScopePlan:
                                    n_sources, check=check)
         if check and n_clamped:  # in a market that feeds no global chain: the compile does not see it
             raise N.BCEError(f"walk scope plan: {n_clamped} sid outside [0, {int(n_sources)})")
-        return cls(pairs, dplan, dentry, dsettle, gsettle, dq, gq, update_global, n_clamped)
+        return cls(pairs, dplan, dentry, dsettle, gsettle, dq, gq, update_global, n_clamped, outcome.contiguous())
+
+    @classmethod
+    def build_lagged(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
+                     market_domain: torch.Tensor, n_sources: int, n_domains: int, forecast_time_us: torch.Tensor,
+                     resolve_time_us: torch.Tensor, update_global: bool = False,
+                     check: bool = True) -> "WalkScopePlan":
+        """:meth:`build` for markets that are forecast at one time and settle at a later one, as
+        :meth:`WalkPlan.build_lagged` (the same times, the same ``ValueError`` from torch checks
+        before the library is touched): market m is read at ``forecast_time_us[m]`` and, if
+        ``outcome[m] >= 0``, its updates run at ``resolve_time_us[m]`` at the scopes of its domain
+        -- the reference as an event loop sorted by (time, market, forecast before resolution).
+
+        The rank of the resolved markets by (resolve time, market) is computed once; both chain
+        families are compiled in that order (:meth:`SettlePlan.build` with ``market_rank``), and
+        one launch of bce_walk_lag_queries per family bisects every query's visible prefix: the
+        global family over ``usid`` and the S sources, the domain family over ``dentry`` and the F
+        chains, its queries only the entries with ``dentry >= 0``.  With ``resolve == forecast``
+        the plan equals :meth:`build`'s, array for array."""
+        M, _, S, _, _ = _check_csr(offsets, sid, n_sources, outcome=outcome, values=False)
+        _check_lag_times(forecast_time_us, resolve_time_us, outcome, M)
+        update_global = bool(update_global)
+        pairs, dplan, dentry, n_clamped = cls._entries(offsets, sid, prob, market_domain, S, n_domains)
+        dentry = dentry.to(torch.int32).contiguous()
+        forecast = forecast_time_us.contiguous()
+        resolve = resolve_time_us.contiguous()
+        rank = _resolve_rank(outcome, resolve)
+        N.require_gpu()
+        masked = torch.where(dplan.market_domain >= 0, outcome, torch.full_like(outcome, -1))
+        dsettle, dq = _lag_family(offsets, dplan.esid, prob, masked, max(dplan.n_entries, 1), check, rank, pairs,
+                                  dentry, forecast, resolve, partial=True)
+        gsettle, gq = _lag_family(offsets, sid, prob, _global_outcome(outcome, dplan.market_domain, update_global),
+                                  n_sources, check, rank, pairs, pairs.usid, forecast, resolve)
+        if check:
+            N.check_faults(offsets.device, "walk scope lag queries")
+            if n_clamped:  # in a market that feeds no global chain: the compile does not see it
+                raise N.BCEError(f"walk scope plan: {n_clamped} sid outside [0, {int(n_sources)})")
+        return cls(pairs, dplan, dentry, dsettle, gsettle, dq, gq, update_global, n_clamped, outcome.contiguous(),
+                   forecast, resolve)
 
 
 @dataclass
@@ -466,20 +558,36 @@ class WalkScopeResult(_ConsensusFields):
     global_correct: torch.Tensor
 
 
-def _walk_scope_read(plan: WalkScopePlan, domains: PairTable, global_table: Optional["ReliabilityTable"],
-                     market_time_us: torch.Tensor, pairs: Optional[PairTable], global_has: Optional[torch.Tensor],
-                     mark_cold: bool, long_min: Optional[int], chunk_bits: Optional[int], half_life_days: float,
-                     min_rel: float):
-    """The launches of :func:`walk_scope_trace`; also returns the raw start rows of the domain
-    chains (:func:`pair_resolve`, None without one) and the ``has`` flags of the global table."""
-    L = N.require_gpu()
+@dataclass
+class _ScopeTraces:
+    """What the read of a namespaced walk starts from: ``raw`` the raw start rows of the domain
+    chains (:func:`pair_resolve`, None without one) and ``dhas`` their "updated_at is truthy";
+    ``dtrace`` / ``gtrace`` the traced states of either family over the entry index (``gtrace``
+    None where no global chain has a bit); ``global_has`` the ``has`` flags of the global table."""
+
+    raw: Optional["PairResolveResult"]  # noqa: F821
+    dhas: Optional[torch.Tensor]
+    dtrace: Optional[torch.Tensor]
+    gtrace: Optional[torch.Tensor]
+    global_has: Optional[torch.Tensor]
+
+
+def _walk_scope_traces(plan: WalkScopePlan, domains: PairTable, global_table: Optional["ReliabilityTable"],
+                       market_time_us: Optional[torch.Tensor], pairs: Optional[PairTable],
+                       global_has: Optional[torch.Tensor], long_min: Optional[int], chunk_bits: Optional[int],
+                       gtrace: torch.Tensor) -> _ScopeTraces:
+    """The argument checks of a namespaced walk and one bce_settle_trace per chain family that
+    has bits: the domain chains from their raw start rows into a buffer of their own, the global
+    chains from the dense table into ``gtrace`` [E, 2].  The states do not depend on the decay
+    parameters; no table is written."""
     pp, dp = plan.pairs, plan.dplan
     S, E, M, F = pp.n_sources, pp.n_entries, pp.n_markets, dp.n_entries
+    _walk_times(plan, market_time_us)
+    N.require_gpu()
     if domains.n_markets != dp.n_markets or domains.n_sources != S:
         raise ValueError("the plan and the domain table describe different batches")
     if pairs is not None and (pairs.n_markets != M or pairs.n_sources != S):
         raise ValueError("the plan and the pair table describe different batches")
-    _check_market_time(market_time_us, M)
     g = global_table
     if g is None and plan.gsettle.n_touched:
         raise ValueError("the batch updates the global scope: global_table is needed")
@@ -491,9 +599,6 @@ def _walk_scope_read(plan: WalkScopePlan, domains: PairTable, global_table: Opti
         assert global_has.dtype == torch.uint8 and global_has.numel() == S, "global_has must be u8[n_sources]"
     dev = pp.esid.device
     st = N.stream(dev)
-    relconf, bits, scope = _entry_buffers(E, dev)  # relconf: the global trace, overwritten in place
-    mtime = market_time_us.contiguous()
-    ent = lambda t: N.ptr(t if E else None)  # noqa: E731
     raw = dhas = dtrace = None
     if F and E:  # the domain chains: start rows by the raw pair lookup over the (domain, source) entries
         raw = pair_resolve(dp.uoffsets, dp.usid, domains, 0, mode="raw", emarket=dp.emarket)
@@ -504,22 +609,56 @@ def _walk_scope_read(plan: WalkScopePlan, domains: PairTable, global_table: Opti
             _settle_trace(plan.dsettle, plan.dq, raw.rel, raw.conf, raw.present, E, dtrace, long_min, chunk_bits, st)
     gtraced = g is not None and plan.gsettle.n_touched > 0
     if gtraced:
-        _settle_trace(plan.gsettle, plan.gq, g.rel, g.conf, g.present, E, relconf, long_min, chunk_bits, st)
-    dom = [N.ptr(x) for x in ((plan.dentry, plan.dq.qlast, dtrace, raw.rel, raw.conf, raw.t_us, dhas)
+        _settle_trace(plan.gsettle, plan.gq, g.rel, g.conf, g.present, E, gtrace, long_min, chunk_bits, st)
+    return _ScopeTraces(raw, dhas, dtrace, gtrace if gtraced else None, global_has)
+
+
+def _walk_scope_launch(plan: WalkScopePlan, tr: _ScopeTraces, global_table: Optional["ReliabilityTable"],
+                       market_time_us: Optional[torch.Tensor], pairs: Optional[PairTable], mark_cold: bool,
+                       half_life_days: float, min_rel: float, relconf: torch.Tensor, bits: torch.Tensor,
+                       scope: torch.Tensor) -> None:
+    """bce_walk_scope_read (a lagged plan: bce_walk_scope_read_lag) from the traces of ``tr`` into
+    ``relconf`` (may be ``tr.gtrace`` itself) / ``bits`` / ``scope``."""
+    L = N.lib()
+    pp, g, raw = plan.pairs, global_table, tr.raw
+    S, E, M, F = pp.n_sources, pp.n_entries, pp.n_markets, plan.dplan.n_entries
+    stamp, now = _walk_times(plan, market_time_us)
+    ent = lambda t: N.ptr(t if E else None)  # noqa: E731
+    if plan.lagged:
+        read, name = L.bce_walk_scope_read_lag, "bce_walk_scope_read_lag"
+        times = (N.ptr(stamp if M else None), N.ptr(now if M else None))
+    else:
+        read, name, times = L.bce_walk_scope_read, "bce_walk_scope_read", (N.ptr(now.contiguous() if M else None),)
+    dom = [N.ptr(x) for x in ((plan.dentry, plan.dq.qlast, tr.dtrace, raw.rel, raw.conf, raw.t_us, tr.dhas)
                               if raw is not None else (None,) * 7)]
-    glo = [N.ptr(x) for x in ((plan.gq.qlast if gtraced else None, relconf if gtraced else None, g.rel, g.conf,
-                               g.t_us, global_has.contiguous()) if g is not None else (None,) * 6)]
-    N.check(L.bce_walk_scope_read(E, ent(pp.usid), ent(pp.emarket), N.ptr(mtime if M else None), M, S,
-                                  N.ptr(pairs.poffsets if pairs is not None else None), *_pair_pointers(pairs),
-                                  pairs.n_rows if pairs is not None else 0, *dom, F if raw is not None else 0, *glo,
-                                  float(half_life_days), float(min_rel), DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE,
-                                  int(bool(mark_cold)), int(plan.n_clamped > 0), N.ptr(relconf), N.ptr(bits),
-                                  N.ptr(scope), st), "bce_walk_scope_read")
-    return SourceTable(relconf, bits, range(E)), scope[:E], raw, global_has  # "names": the entry indices
+    gtraced = tr.gtrace is not None
+    glo = [N.ptr(x) for x in ((plan.gq.qlast if gtraced else None, tr.gtrace, g.rel, g.conf, g.t_us,
+                               tr.global_has.contiguous()) if g is not None else (None,) * 6)]
+    N.check(read(E, ent(pp.usid), ent(pp.emarket), *times, M, S,
+                 N.ptr(pairs.poffsets if pairs is not None else None), *_pair_pointers(pairs),
+                 pairs.n_rows if pairs is not None else 0, *dom, F if raw is not None else 0, *glo,
+                 float(half_life_days), float(min_rel), DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE, int(bool(mark_cold)),
+                 int(plan.n_clamped > 0), N.ptr(relconf), N.ptr(bits), N.ptr(scope),
+                 N.stream(pp.esid.device)), name)
+
+
+def _walk_scope_read(plan: WalkScopePlan, domains: PairTable, global_table: Optional["ReliabilityTable"],
+                     market_time_us: Optional[torch.Tensor], pairs: Optional[PairTable],
+                     global_has: Optional[torch.Tensor], mark_cold: bool, long_min: Optional[int],
+                     chunk_bits: Optional[int], half_life_days: float, min_rel: float):
+    """The launches of :func:`walk_scope_trace`; also returns the raw start rows of the domain
+    chains (:func:`pair_resolve`, None without one) and the ``has`` flags of the global table."""
+    E = plan.pairs.n_entries
+    relconf, bits, scope = _entry_buffers(E, plan.pairs.esid.device)  # relconf: the global trace, overwritten in place
+    tr = _walk_scope_traces(plan, domains, global_table, market_time_us, pairs, global_has, long_min, chunk_bits,
+                            relconf)
+    _walk_scope_launch(plan, tr, global_table, market_time_us, pairs, mark_cold, half_life_days, min_rel, relconf,
+                       bits, scope)
+    return SourceTable(relconf, bits, range(E)), scope[:E], tr.raw, tr.global_has  # "names": the entry indices
 
 
 def walk_scope_trace(plan: WalkScopePlan, domains: PairTable, global_table: Optional["ReliabilityTable"],
-                     market_time_us: torch.Tensor, *, pairs: Optional[PairTable] = None,
+                     market_time_us: Optional[torch.Tensor] = None, *, pairs: Optional[PairTable] = None,
                      global_has: Optional[torch.Tensor] = None, mark_cold: bool = False,
                      long_min: Optional[int] = None, chunk_bits: Optional[int] = None,
                      half_life_days: float = DECAY_HALF_LIFE_DAYS, min_rel: float = DECAY_MINIMUM):
@@ -528,13 +667,13 @@ def walk_scope_trace(plan: WalkScopePlan, domains: PairTable, global_table: Opti
     global chains from the dense table), then bce_walk_scope_read.  Returns the consensus table
     over the entry index -- every entry's namespaced ``get_reliability(apply_decay=True)`` at its
     market's time, after the earlier markets were settled -- and ``scope`` u8[E] (NS_* codes).
-    No table is written."""
+    No table is written.  ``market_time_us``: as :func:`walk_forward_scoped`."""
     return _walk_scope_read(plan, domains, global_table, market_time_us, pairs, global_has, mark_cold, long_min,
                             chunk_bits, half_life_days, min_rel)[:2]
 
 
 def walk_forward_scoped(plan: WalkScopePlan, domains: PairTable, global_table: Optional["ReliabilityTable"],
-                        market_time_us: torch.Tensor, *, offsets: torch.Tensor, prob: torch.Tensor,
+                        market_time_us: Optional[torch.Tensor] = None, *, offsets: torch.Tensor, prob: torch.Tensor,
                         pairs: Optional[PairTable] = None, global_has: Optional[torch.Tensor] = None,
                         mark_cold: bool = False, mode: str = "exact", long_min: Optional[int] = None,
                         chunk_bits: Optional[int] = None, commit: bool = True,
@@ -562,10 +701,18 @@ def walk_forward_scoped(plan: WalkScopePlan, domains: PairTable, global_table: O
     :class:`PairTable` (``result.domains``; ``domains`` itself is never written); the global table
     is settled in place as :func:`walk_forward` leaves it, ``global_has`` set for the touched
     sources.  ``commit=False`` leaves every input untouched.  The result does not depend on
-    ``long_min`` / ``chunk_bits``."""
+    ``long_min`` / ``chunk_bits``.
+
+    A plan from :meth:`WalkScopePlan.build_lagged` takes its times from the plan
+    (``market_time_us`` stays None; passing one as well, or none for an ordinary plan,
+    ``ValueError``): market m is read at its forecast time and settled at its resolve time, a
+    scope exists for an entry when a bit of its chain resolved before the entry's forecast or its
+    start row has ``has``, and every state and every committed row is stamped with the resolve
+    time of the market of its chain's last bit."""
     pp = plan.pairs
     if offsets.numel() - 1 != pp.n_markets or prob.numel() != pp.esid.numel():
         raise ValueError("offsets / prob are not the batch the plan was built from")
+    stamp, _ = _walk_times(plan, market_time_us)
     wtable, scope, raw, ghas = _walk_scope_read(plan, domains, global_table, market_time_us, pairs, global_has,
                                                 mark_cold, long_min, chunk_bits, DECAY_HALF_LIFE_DAYS, DECAY_MINIMUM)
     res = consensus(offsets, pp.esid, prob.to(torch.float64), wtable, mode=mode, **_bins_as_plan(consensus_kwargs))
@@ -573,12 +720,12 @@ def walk_forward_scoped(plan: WalkScopePlan, domains: PairTable, global_table: O
     new_domains = domains
     if commit:
         if ds.n_touched and raw is not None:
-            _commit_chains(ds, raw.rel, raw.conf, raw.t_us, raw.present, plan.dq.slast, market_time_us, long_min,
+            _commit_chains(ds, raw.rel, raw.conf, raw.t_us, raw.present, plan.dq.slast, stamp, long_min,
                            chunk_bits)
             new_domains = _pair_merge(plan.dplan, domains, raw, ds.total[:plan.dplan.n_entries] > 0)
         if gs.n_touched:
             g = global_table
-            touched = _commit_chains(gs, g.rel, g.conf, g.t_us, g.present, plan.gq.slast, market_time_us, long_min,
+            touched = _commit_chains(gs, g.rel, g.conf, g.t_us, g.present, plan.gq.slast, stamp, long_min,
                                      chunk_bits)
             if ghas is not g.present:
                 ghas.index_fill_(0, touched, 1)

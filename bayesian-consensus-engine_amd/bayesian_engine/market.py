@@ -416,6 +416,47 @@ class WalkScore:
     sources: Dict[str, SourceScore]
 
 
+def _keyed_results(keyed, results) -> Dict[str, Dict[str, Any]]:
+    """The result dicts of a walk keyed by ``str(market.id)``, in walk order."""
+    out = {}
+    for (_, _, m, _), r in zip(keyed, results):
+        r["marketId"] = str(m.id)
+        out[str(m.id)] = r
+    return out
+
+
+def _sweep_arguments(what: str, store, half_life_days, min_rel, n_bins):
+    """The checked arguments of a decay sweep: ``(half_life_days, min_rel, n_bins)``."""
+    if not isinstance(store, NamespacedReliabilityStore):
+        raise TypeError(f"{what} needs a NamespacedReliabilityStore (got {type(store).__name__})")
+    try:
+        hl, mr = [float(x) for x in half_life_days], [float(x) for x in min_rel]
+    except TypeError:
+        raise TypeError("half_life_days and min_rel must be sequences of numbers") from None
+    if not hl or not mr:
+        raise ValueError(f"{what} needs at least one half_life_days and one min_rel")
+    if any(not h > 0 for h in hl):
+        raise ValueError(f"half_life_days must be > 0 (got {hl})")
+    if any(not 0.0 <= m <= 1.0 for m in mr):
+        raise ValueError(f"min_rel must be in [0, 1] (got {mr})")
+    B = int(n_bins)
+    if not 1 <= B <= batch.SCORE_MAX_BINS:
+        raise ValueError(f"n_bins must be in [1, {batch.SCORE_MAX_BINS}] (got {n_bins})")
+    return hl, mr, B
+
+
+def _sweep_rows(scores, hl, mr, B) -> List["BacktestScore"]:
+    """One :class:`BacktestScore` per grid point of a store sweep (None: a history without signals)."""
+    params = [{"half_life_days": h, "min_rel": m} for h in hl for m in mr]
+    if scores is None:
+        return [BacktestScore.empty(B, p) for p in params]
+    flat = batch.ScoreResult(*(getattr(scores, k)[:, 0] for k in ("counts", "sums", "bin_n", "bin_pos", "bin_psum")))
+    rows = BacktestScore.from_result(flat)
+    for r, p in zip(rows, params):
+        r.params = p
+    return rows
+
+
 class CrossMarketAggregator:
     """Aggregate data across multiple markets (market.py:244-408)."""
 
@@ -570,9 +611,11 @@ class CrossMarketAggregator:
         store position), and a market reads only the outcomes that had arrived by its forecast
         (``store.walk_forward(resolve_times=)``).  A resolved market whose ``resolved_at`` is
         missing or earlier than its ``created_at`` is a ``ValueError`` that names it.  The lagged
-        walk is single-scope: together with ``domain_of=``, ``ValueError``."""
+        walk here is single-scope: together with ``domain_of=``, ``ValueError``
+        (:meth:`walk_forward_namespaced` walks a history that spans domains with lag)."""
         if lagged and domain_of is not None:
-            raise ValueError("lagged=True walks one scope: it cannot be combined with domain_of=")
+            raise ValueError("lagged=True walks one scope: it cannot be combined with domain_of= "
+                             "(walk_forward_namespaced(lagged=True) does that)")
         if domain_of is not None:
             if domain is not None:
                 raise ValueError("domain= (one for the batch) and domain_of= (one per market) exclude each other")
@@ -588,11 +631,39 @@ class CrossMarketAggregator:
                 update_global=update_global, dry_run=dry_run)
         else:
             results, summary = store.walk_forward(batch_markets, stamps, domain=domain, dry_run=dry_run)
-        out = {}
-        for (_, _, m, _), r in zip(keyed, results):
-            r["marketId"] = str(m.id)
-            out[str(m.id)] = r
-        return out, summary
+        return _keyed_results(keyed, results), summary
+
+    def walk_forward_namespaced(self, store, domain_of, patterns: Optional[List[str]] = None,
+                                update_global: bool = False, market_scope: bool = False, lagged: bool = False,
+                                dry_run: bool = False, device_match: Optional[bool] = None):
+        """:meth:`walk_forward` over a history that spans domains (``domain_of`` as there: a
+        callable or "category"), immediate or ``lagged``: every market is read with the fallback
+        market -> domain -> global -> cold start as the rows stood at its forecast, and a
+        resolved one is settled at the scope of its own domain (``update_global`` as
+        ``update_reliability`` takes it; ``market_scope=True`` reads seeded (source, market) rows
+        first).  ``lagged=False`` returns exactly what ``walk_forward(domain_of=)`` returns;
+        ``lagged=True`` forecasts every market at ``created_at`` and settles it at
+        ``resolved_at``, so no read sees an outcome that had not arrived
+        (``store.walk_forward_namespaced(resolve_times=)``).  Returns ``(results, summary)`` as
+        :meth:`walk_forward`; ``score_walk`` takes the results."""
+        if not isinstance(store, NamespacedReliabilityStore):
+            raise TypeError(f"walk_forward_namespaced needs a NamespacedReliabilityStore (got {type(store).__name__})")
+        keyed, batch_markets, stamps, resolve_stamps, kw = self._namespaced_history(
+            domain_of, patterns, update_global, market_scope, lagged, device_match)
+        results, summary = store.walk_forward_namespaced(batch_markets, stamps, dry_run=dry_run,
+                                                         resolve_times=resolve_stamps, **kw)
+        return _keyed_results(keyed, results), summary
+
+    def _namespaced_history(self, domain_of, patterns, update_global, market_scope, lagged, device_match):
+        """:meth:`_walk_history` plus the keyword arguments the namespaced store methods share."""
+        if domain_of is None:
+            raise ValueError("domain_of is needed: a callable market -> domain, or \"category\"")
+        domain_of = _domain_fn(domain_of)
+        keyed, batch_markets, stamps, resolve_stamps = self._walk_history(patterns, device_match, lagged)
+        kw = dict(domains=[domain_of(m) for _, _, m, _ in keyed],
+                  market_ids=[str(m.id) for _, _, m, _ in keyed] if market_scope else None,
+                  update_global=update_global)
+        return keyed, batch_markets, stamps, resolve_stamps, kw
 
     def _walk_history(self, patterns: Optional[List[str]], device_match: Optional[bool], lagged: bool = False):
         """The markets of a back-test in walk order: ``(keyed, batch_markets, stamps,
@@ -734,33 +805,27 @@ class CrossMarketAggregator:
         settlement trace does not depend on the decay parameters, so it runs once
         (``store.sweep_decay``, ``batch.walk_sweep``); nothing is written to the store.  The
         single-scope walk only: a history that spans domains (``walk_forward(domain_of=)``) is
-        not swept here.  ``lagged`` as in ``walk_forward``."""
-        if not isinstance(store, NamespacedReliabilityStore):
-            raise TypeError(f"sweep_decay needs a NamespacedReliabilityStore (got {type(store).__name__})")
-        try:
-            hl, mr = [float(x) for x in half_life_days], [float(x) for x in min_rel]
-        except TypeError:
-            raise TypeError("half_life_days and min_rel must be sequences of numbers") from None
-        if not hl or not mr:
-            raise ValueError("sweep_decay needs at least one half_life_days and one min_rel")
-        if any(not h > 0 for h in hl):
-            raise ValueError(f"half_life_days must be > 0 (got {hl})")
-        if any(not 0.0 <= m <= 1.0 for m in mr):
-            raise ValueError(f"min_rel must be in [0, 1] (got {mr})")
-        B = int(n_bins)
-        if not 1 <= B <= batch.SCORE_MAX_BINS:
-            raise ValueError(f"n_bins must be in [1, {batch.SCORE_MAX_BINS}] (got {n_bins})")
+        swept by :meth:`sweep_decay_namespaced`.  ``lagged`` as in ``walk_forward``."""
+        hl, mr, B = _sweep_arguments("sweep_decay", store, half_life_days, min_rel, n_bins)
         _, batch_markets, stamps, resolve_stamps = self._walk_history(patterns, device_match, lagged)
-        params = [{"half_life_days": h, "min_rel": m} for h in hl for m in mr]
         scores = store.sweep_decay(batch_markets, stamps, hl, mr, domain=domain, n_bins=B,
                                    resolve_times=resolve_stamps)
-        if scores is None:
-            return [BacktestScore.empty(B, p) for p in params]
-        flat = batch.ScoreResult(*(getattr(scores, k)[:, 0] for k in ("counts", "sums", "bin_n", "bin_pos", "bin_psum")))
-        rows = BacktestScore.from_result(flat)
-        for r, p in zip(rows, params):
-            r.params = p
-        return rows
+        return _sweep_rows(scores, hl, mr, B)
+
+    def sweep_decay_namespaced(self, store, half_life_days, min_rel, domain_of, patterns: Optional[List[str]] = None,
+                               update_global: bool = False, market_scope: bool = False, lagged: bool = False,
+                               n_bins: int = 10, device_match: Optional[bool] = None) -> List["BacktestScore"]:
+        """:meth:`sweep_decay` over the namespaced walk: the back-test of
+        ``walk_forward_namespaced(store, domain_of, ..., dry_run=True)``, immediate or ``lagged``,
+        for every point of the grid, one whole-history :class:`BacktestScore` per point
+        (``params`` names it).  Both chain families are traced once
+        (``store.sweep_decay_namespaced``, ``batch.walk_sweep_scoped``); nothing is written."""
+        hl, mr, B = _sweep_arguments("sweep_decay_namespaced", store, half_life_days, min_rel, n_bins)
+        _, batch_markets, stamps, resolve_stamps, kw = self._namespaced_history(
+            domain_of, patterns, update_global, market_scope, lagged, device_match)
+        scores = store.sweep_decay_namespaced(batch_markets, stamps, hl, mr, n_bins=B, resolve_times=resolve_stamps,
+                                              **kw)
+        return _sweep_rows(scores, hl, mr, B)
 
     def summarize_category(self, category: str) -> Dict[str, Any]:
         markets = self._store.list_markets(pattern=f"{category}:*")

@@ -481,9 +481,59 @@ class NamespacedReliabilityStore:
         N.check_faults(dev, "sweep_decay")
         return scores
 
+    def _namespaced_walk(self, markets, times, domains, market_ids, update_global, resolve_times):
+        """What :meth:`walk_forward_namespaced` and :meth:`sweep_decay_namespaced` share: the
+        argument checks, the interned batch, the compiled :class:`batch.WalkScopePlan` (lagged
+        where ``resolve_times`` is given) and the three loaded scopes, as a dict; None for a
+        history without signals (``markets`` / ``domains`` normalised either way, as the first
+        two items of the returned tuple)."""
+        markets = [(list(signals), outcome) for signals, outcome in markets]
+        M = len(markets)
+        t_us, r_us = _walk_times_us(markets, times, resolve_times)
+        domains = [domains] * M if isinstance(domains, str) or domains is None else list(domains)
+        if len(domains) != M:
+            raise ValueError(f"domains has {len(domains)} entries for {M} markets")
+        if market_ids is not None:
+            market_ids = [str(m) for m in market_ids]
+            if len(market_ids) != M:
+                raise ValueError(f"market_ids has {len(market_ids)} entries for {M} markets")
+            if not all(market_ids):
+                raise ValueError("every market id must be truthy (a falsy one selects another scope)")
+            if len(set(market_ids)) != M:
+                raise ValueError("duplicate market id in market_ids")
+        rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
+        names = list(rank)
+        if not names:
+            return markets, domains, None
+        offsets, sid, prob = signals_csr([signals for signals, _ in markets], rank)
+        outcome = _outcome_codes(markets)
+        dnames = list(dict.fromkeys(d for d in domains if d))
+        drank = {d: i for i, d in enumerate(dnames)}
+        market_domain = np.array([drank[d] if d else -1 for d in domains], np.int32)
+        N.require_gpu()
+        dev = N.device()
+        T = batch.to_device(dev)
+        off, prob = T(offsets), T(prob)
+        build = (T(sid), prob, T(outcome), T(market_domain), len(names), len(dnames))
+        if r_us is None:
+            plan, mtime = batch.WalkScopePlan.build(off, *build, update_global=update_global), T(t_us)
+        else:
+            plan, mtime = batch.WalkScopePlan.build_lagged(off, *build, T(t_us), T(r_us),
+                                                           update_global=update_global), None
+        dkeys = [f"__domain__:{d}" for d in dnames]
+        dtable = self._store.load_pair_table(dkeys, names, device=dev)
+        ptable = self._store.load_pair_table(market_ids, names, device=dev) if market_ids is not None else None
+        gtable = self._store.load_table(self.GLOBAL_MARKET_ID, names, device=dev)
+        stamps = self._store.fetch_pairs([(n, self.GLOBAL_MARKET_ID) for n in names])
+        ghas = T(np.array([1 if stamps.get((n, self.GLOBAL_MARKET_ID), (0, 0, ""))[2] else 0 for n in names],
+                          np.uint8))
+        return markets, domains, dict(names=names, dnames=dnames, dkeys=dkeys, offsets=offsets, off=off, prob=prob,
+                                      plan=plan, mtime=mtime, dtable=dtable, ptable=ptable, gtable=gtable, ghas=ghas,
+                                      dev=dev)
+
     def walk_forward_namespaced(self, markets: Sequence[tuple], times: Sequence, domains=None,
                                 market_ids: Optional[Sequence[str]] = None, update_global: bool = False,
-                                dry_run: bool = False):
+                                dry_run: bool = False, resolve_times: Optional[Sequence] = None):
         """:meth:`walk_forward` for a history that spans domains, with the fallback chain at
         every read, as ONE compiled batch (:func:`batch.walk_forward_scoped`): market i is scored
         by ``compute_consensus`` with every source fetched by ``get_reliability(sid,
@@ -498,50 +548,21 @@ class NamespacedReliabilityStore:
         global rows written back with one ``executemany``, each with its own ``updated_at``,
         unless ``dry_run``.  Returns ``(results, summary)``: one dict per market shaped like
         ``compute_consensus``'s, and a :class:`SettleSummary` keyed as
-        ``settle_markets(domains=)`` keys it (``(source_id, domain-or-None)``)."""
-        markets = [(list(signals), outcome) for signals, outcome in markets]
-        times = list(times)
-        M = len(markets)
-        if len(times) != M:
-            raise ValueError(f"times has {len(times)} entries for {M} markets")
-        t_us = np.array([iso_to_us(t) if isinstance(t, str) else dt_to_us(t) for t in times], np.int64)
-        if (t_us == NO_TIMESTAMP).any():
-            raise ValueError("a market time is empty or unparseable")
-        domains = [domains] * M if isinstance(domains, str) or domains is None else list(domains)
-        if len(domains) != M:
-            raise ValueError(f"domains has {len(domains)} entries for {M} markets")
-        if market_ids is not None:
-            market_ids = [str(m) for m in market_ids]
-            if len(market_ids) != M:
-                raise ValueError(f"market_ids has {len(market_ids)} entries for {M} markets")
-            if not all(market_ids):
-                raise ValueError("every market id must be truthy (a falsy one selects another scope)")
-            if len(set(market_ids)) != M:
-                raise ValueError("duplicate market id in market_ids")
-        rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
-        names = list(rank)
-        offsets, sid, prob = signals_csr([signals for signals, _ in markets], rank)
-        outcome = _outcome_codes(markets)
-        if not names:
+        ``settle_markets(domains=)`` keys it (``(source_id, domain-or-None)``).
+
+        ``resolve_times`` as in :meth:`walk_forward`: market i is scored at ``times[i]`` and its
+        updates run, and stamp the rows of its scopes, at ``resolve_times[i]``, so a scope that
+        had no truthy stamp when a market was forecast is skipped by that read even if an
+        earlier-listed market creates it later (:meth:`batch.WalkScopePlan.build_lagged`); rows
+        written back carry the resolve time of their last settling market, per scope."""
+        markets, domains, b = self._namespaced_walk(markets, times, domains, market_ids, update_global,
+                                                    resolve_times)
+        if b is None:
             return [core_no_signals() for _ in markets], SettleSummary({}, {}, {}, {})
-        dnames = list(dict.fromkeys(d for d in domains if d))
-        drank = {d: i for i, d in enumerate(dnames)}
-        market_domain = np.array([drank[d] if d else -1 for d in domains], np.int32)
-        N.require_gpu()
-        dev = N.device()
-        T = batch.to_device(dev)
-        off, prob = T(offsets), T(prob)
-        plan = batch.WalkScopePlan.build(off, T(sid), prob, T(outcome), T(market_domain), len(names), len(dnames),
-                                         update_global=update_global)
-        dkeys = [f"__domain__:{d}" for d in dnames]
-        dtable = self._store.load_pair_table(dkeys, names, device=dev)
-        ptable = self._store.load_pair_table(market_ids, names, device=dev) if market_ids is not None else None
-        gtable = self._store.load_table(self.GLOBAL_MARKET_ID, names, device=dev)
-        stamps = self._store.fetch_pairs([(n, self.GLOBAL_MARKET_ID) for n in names])
-        ghas = T(np.array([1 if stamps.get((n, self.GLOBAL_MARKET_ID), (0, 0, ""))[2] else 0 for n in names],
-                          np.uint8))
-        res = batch.walk_forward_scoped(plan, dtable, gtable, T(t_us), offsets=off, prob=prob, pairs=ptable,
-                                        global_has=ghas, validate=False)
+        names, dnames, dkeys, offsets, off, prob, plan, dtable, gtable, dev = (
+            b[k] for k in ("names", "dnames", "dkeys", "offsets", "off", "prob", "plan", "dtable", "gtable", "dev"))
+        res = batch.walk_forward_scoped(plan, dtable, gtable, b["mtime"], offsets=off, prob=prob, pairs=b["ptable"],
+                                        global_has=b["ghas"], validate=False)
         N.check_faults(dev, "walk_forward_namespaced")
         results = _walk_dicts(markets, offsets, names, res, plan.pairs)
         records, global_records, rows = {}, {}, []
@@ -571,6 +592,25 @@ class NamespacedReliabilityStore:
         if not dry_run and rows:
             self._store._upsert(rows)
         return results, SettleSummary(records, global_records, total, correct)
+
+    def sweep_decay_namespaced(self, markets: Sequence[tuple], times: Sequence, half_life_days: Sequence[float],
+                               min_rel: Sequence[float], domains=None, market_ids: Optional[Sequence[str]] = None,
+                               update_global: bool = False, n_bins: int = 10,
+                               resolve_times: Optional[Sequence] = None):
+        """:meth:`walk_forward_namespaced` as a dry run for every point of a grid of decay
+        parameters, each scored against the batch's outcomes (:func:`batch.walk_sweep_scoped`:
+        neither chain family depends on the decay parameters, so both are traced once).  Nothing
+        is written.  Returns the :class:`batch.ScoreResult` of the whole history with a leading
+        grid dimension ``[len(half_life_days) * len(min_rel), 1, ...]`` (``min_rel`` fastest), or
+        None for a history without signals.  ``resolve_times`` as :meth:`walk_forward_namespaced`."""
+        _, _, b = self._namespaced_walk(markets, times, domains, market_ids, update_global, resolve_times)
+        if b is None:
+            return None
+        scores, _ = batch.walk_sweep_scoped(b["plan"], b["dtable"], b["gtable"], b["mtime"], offsets=b["off"],
+                                            prob=b["prob"], half_life_days=half_life_days, min_rel=min_rel,
+                                            pairs=b["ptable"], global_has=b["ghas"], n_bins=n_bins)
+        N.check_faults(b["dev"], "sweep_decay_namespaced")
+        return scores
 
     def get_reliability_many(self, names: Sequence[str], market_id: Optional[str] = None,
                              domain: Optional[str] = None, apply_decay: bool = True,

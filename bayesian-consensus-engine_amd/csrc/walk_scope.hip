@@ -15,7 +15,10 @@
 //                           market's segment), else the entry's domain chain, else its global chain,
 //                           else the cold start; the picked state decayed from its own stamp to the
 //                           entry's market time, packed as the consensus table over the entry index,
-//                           the present bits from one ballot per wave as walk_read_kernel.
+//                           the present bits from one ballot per wave as walk_read_kernel.  With
+//                           resolution lag a traced state is stamped with the RESOLVE time of market
+//                           qlast and the entry is read at its market's FORECAST time
+//                           (bce_walk_scope_read_lag); otherwise the two are one array.
 #include "scope_lookup.hpp"
 
 #pragma clang fp contract(off)
@@ -26,7 +29,8 @@ struct WalkScopeArgs {
   int64_t E;
   const int32_t* usid;      // [E] source of every entry
   const int32_t* emarket;   // [E]
-  const int64_t* mtime;     // [M]
+  const int64_t* stamp;     // [M] the time a market's updates stamp updated_at with
+  const int64_t* now;       // [M] the time a market is read at (the same array without resolution lag)
   int64_t M;
   int32_t S;
   const int64_t* poffsets;  // [M + 1] NULL: no market scope (market_id=None)
@@ -103,7 +107,7 @@ __global__ __launch_bounds__(256) void walk_scope_read_kernel(WalkScopeArgs a) {
           const double2 st = a.dtrace[e];
           r = st.x;
           c = st.y;
-          t = a.mtime[dql];
+          t = a.stamp[dql];
           sc = 1;
         } else if (a.dstart.has[f]) {
           r = a.dstart.rel[f];
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(256) void walk_scope_read_kernel(WalkScopeArgs a) {
           const double2 st = a.gtrace[e];
           r = st.x;
           c = st.y;
-          t = a.mtime[gql];
+          t = a.stamp[gql];
           sc = 2;
         } else if (a.gstart.has[s]) {
           r = a.gstart.rel[s];
@@ -129,7 +133,7 @@ __global__ __launch_bounds__(256) void walk_scope_read_kernel(WalkScopeArgs a) {
       }
       if (sc != 3) {  // 4. else the cold start, undecayed
         DecayConst k = a.k;
-        k.now_us = a.mtime[m];
+        k.now_us = a.now[m];
         r = decayed(r, t, k, sExp);
       }
       a.relconf[e] = make_double2(r, c);
@@ -144,24 +148,26 @@ __global__ __launch_bounds__(256) void walk_scope_read_kernel(WalkScopeArgs a) {
 
 using namespace bce;
 
-extern "C" int bce_walk_scope_read(int64_t n_entries, const int32_t* usid, const int32_t* emarket,
-                                   const int64_t* market_time_us, int64_t n_markets, int32_t n_sources,
-                                   const int64_t* poffsets, const int32_t* psid, const double* prel,
-                                   const double* pconf, const int64_t* pt_us, const uint8_t* phas, int64_t n_rows,
-                                   const int32_t* dentry, const int32_t* dqlast, const double* dtrace,
-                                   const double* drel, const double* dconf, const int64_t* dt_us,
-                                   const uint8_t* dhas, int64_t n_dentries, const int32_t* gqlast,
-                                   const double* gtrace, const double* grel, const double* gconf,
-                                   const int64_t* gt_us, const uint8_t* ghas, double half_life_days, double min_rel,
-                                   double default_rel, double default_conf, int mark_cold, int sid_clamped,
-                                   double* relconf, uint32_t* present_bits, uint8_t* scope, void* stream) {
+// bce_walk_scope_read and bce_walk_scope_read_lag: one kernel, the two time arrays equal without lag.
+static int walk_scope_read_launch(int64_t n_entries, const int32_t* usid, const int32_t* emarket,
+                                  const int64_t* stamp_time_us, const int64_t* market_time_us, int64_t n_markets,
+                                  int32_t n_sources, const int64_t* poffsets, const int32_t* psid,
+                                  const double* prel, const double* pconf, const int64_t* pt_us, const uint8_t* phas,
+                                  int64_t n_rows, const int32_t* dentry, const int32_t* dqlast, const double* dtrace,
+                                  const double* drel, const double* dconf, const int64_t* dt_us,
+                                  const uint8_t* dhas, int64_t n_dentries, const int32_t* gqlast,
+                                  const double* gtrace, const double* grel, const double* gconf,
+                                  const int64_t* gt_us, const uint8_t* ghas, double half_life_days, double min_rel,
+                                  double default_rel, double default_conf, int mark_cold, int sid_clamped,
+                                  double* relconf, uint32_t* present_bits, uint8_t* scope, void* stream) {
   BCE_REQUIRE(n_entries >= 0 && n_markets >= 0 && n_sources > 0 && n_rows >= 0 && n_dentries >= 0,
               "walk_scope_read: bad shape");
   BCE_REQUIRE(n_entries < (1ll << 31) && n_markets < (1ll << 31) && n_dentries < (1ll << 31),
               "walk_scope_read: n_entries, n_markets or n_dentries >= 2^31");
   BCE_REQUIRE(n_markets > 0 || n_entries == 0, "walk_scope_read: entries without markets");
   if (n_entries == 0 && !sid_clamped) return BCE_OK;
-  BCE_REQUIRE(n_entries == 0 || (usid && emarket && market_time_us), "walk_scope_read: NULL argument");
+  BCE_REQUIRE(n_entries == 0 || (usid && emarket && stamp_time_us && market_time_us),
+              "walk_scope_read: NULL argument");
   BCE_REQUIRE(n_entries == 0 || (relconf && present_bits && scope), "walk_scope_read: NULL output");
   BCE_REQUIRE(poffsets || n_rows == 0, "walk_scope_read: market rows without poffsets");
   if (n_rows > 0) {
@@ -181,7 +187,8 @@ extern "C" int bce_walk_scope_read(int64_t n_entries, const int32_t* usid, const
   a.E = n_entries;
   a.usid = usid;
   a.emarket = emarket;
-  a.mtime = market_time_us;
+  a.stamp = stamp_time_us;
+  a.now = market_time_us;
   a.M = n_markets;
   a.S = n_sources;
   a.poffsets = poffsets;
@@ -207,4 +214,41 @@ extern "C" int bce_walk_scope_read(int64_t n_entries, const int32_t* usid, const
   hipLaunchKernelGGL(walk_scope_read_kernel, dim3((unsigned)(g < 1 ? 1 : (g < kLookupGridCap ? g : kLookupGridCap))),
                      dim3(256), 0, as_stream(stream), a);
   return check_launch("walk_scope_read_kernel");
+}
+
+extern "C" int bce_walk_scope_read(int64_t n_entries, const int32_t* usid, const int32_t* emarket,
+                                   const int64_t* market_time_us, int64_t n_markets, int32_t n_sources,
+                                   const int64_t* poffsets, const int32_t* psid, const double* prel,
+                                   const double* pconf, const int64_t* pt_us, const uint8_t* phas, int64_t n_rows,
+                                   const int32_t* dentry, const int32_t* dqlast, const double* dtrace,
+                                   const double* drel, const double* dconf, const int64_t* dt_us,
+                                   const uint8_t* dhas, int64_t n_dentries, const int32_t* gqlast,
+                                   const double* gtrace, const double* grel, const double* gconf,
+                                   const int64_t* gt_us, const uint8_t* ghas, double half_life_days, double min_rel,
+                                   double default_rel, double default_conf, int mark_cold, int sid_clamped,
+                                   double* relconf, uint32_t* present_bits, uint8_t* scope, void* stream) {
+  return walk_scope_read_launch(n_entries, usid, emarket, market_time_us, market_time_us, n_markets, n_sources,
+                                poffsets, psid, prel, pconf, pt_us, phas, n_rows, dentry, dqlast, dtrace, drel, dconf,
+                                dt_us, dhas, n_dentries, gqlast, gtrace, grel, gconf, gt_us, ghas, half_life_days,
+                                min_rel, default_rel, default_conf, mark_cold, sid_clamped, relconf, present_bits,
+                                scope, stream);
+}
+
+extern "C" int bce_walk_scope_read_lag(int64_t n_entries, const int32_t* usid, const int32_t* emarket,
+                                       const int64_t* stamp_time_us, const int64_t* now_time_us, int64_t n_markets,
+                                       int32_t n_sources, const int64_t* poffsets, const int32_t* psid,
+                                       const double* prel, const double* pconf, const int64_t* pt_us,
+                                       const uint8_t* phas, int64_t n_rows, const int32_t* dentry,
+                                       const int32_t* dqlast, const double* dtrace, const double* drel,
+                                       const double* dconf, const int64_t* dt_us, const uint8_t* dhas,
+                                       int64_t n_dentries, const int32_t* gqlast, const double* gtrace,
+                                       const double* grel, const double* gconf, const int64_t* gt_us,
+                                       const uint8_t* ghas, double half_life_days, double min_rel, double default_rel,
+                                       double default_conf, int mark_cold, int sid_clamped, double* relconf,
+                                       uint32_t* present_bits, uint8_t* scope, void* stream) {
+  return walk_scope_read_launch(n_entries, usid, emarket, stamp_time_us, now_time_us, n_markets, n_sources, poffsets,
+                                psid, prel, pconf, pt_us, phas, n_rows, dentry, dqlast, dtrace, drel, dconf, dt_us,
+                                dhas, n_dentries, gqlast, gtrace, grel, gconf, gt_us, ghas, half_life_days, min_rel,
+                                default_rel, default_conf, mark_cold, sid_clamped, relconf, present_bits, scope,
+                                stream);
 }

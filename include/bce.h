@@ -542,7 +542,27 @@ int bce_walk_read_lag(int64_t n_entries, const int32_t* usid, const int32_t* ema
  * No input makes the kernel read or write outside its arrays: an emarket, dqlast or gqlast outside
  * the batch (read as market 0 / "no earlier bit"), a dentry outside [-1, n_dentries) (read as -1)
  * and market-row offsets that are no segment of [0, n_rows] (searched as empty) raise the fault
- * word; a usid outside [0, n_sources) is clamped and raises it, as does sid_clamped != 0. */
+ * word; a usid outside [0, n_sources) is clamped and raises it, as does sid_clamped != 0.
+ *
+ * bce_walk_scope_read_lag: bce_walk_scope_read with two time arrays in market_time_us's place, for
+ * a batch with resolution lag: dtrace[e] / gtrace[e] are stamped with stamp_time_us[dqlast[e]] /
+ * stamp_time_us[gqlast[e]] (the RESOLVE time of the market of the last visible bit) and the picked
+ * state is decayed to now_time_us[m] (the FORECAST time of the entry's market).  dqlast / gqlast
+ * are then the qlast of bce_walk_lag_queries, launched once per chain family: the global family
+ * with usid as the chain of an entry over n_sources chains, the domain family with dentry as the
+ * chain of an entry over n_dentries chains and a qentry that lists only the entries with
+ * dentry >= 0 (qlast pre-filled with -1).  One kernel serves both entries: bce_walk_scope_read
+ * passes its one array twice.  Same checks, same fault rules, both arrays non-NULL. */
+int bce_walk_scope_read_lag(int64_t n_entries, const int32_t* usid, const int32_t* emarket,
+                            const int64_t* stamp_time_us, const int64_t* now_time_us, int64_t n_markets,
+                            int32_t n_sources, const int64_t* poffsets, const int32_t* psid, const double* prel,
+                            const double* pconf, const int64_t* pt_us, const uint8_t* phas, int64_t n_rows,
+                            const int32_t* dentry, const int32_t* dqlast, const double* dtrace, const double* drel,
+                            const double* dconf, const int64_t* dt_us, const uint8_t* dhas, int64_t n_dentries,
+                            const int32_t* gqlast, const double* gtrace, const double* grel, const double* gconf,
+                            const int64_t* gt_us, const uint8_t* ghas, double half_life_days, double min_rel,
+                            double default_rel, double default_conf, int mark_cold, int sid_clamped,
+                            double* relconf, uint32_t* present_bits, uint8_t* scope, void* stream);
 int bce_walk_scope_read(int64_t n_entries, const int32_t* usid, const int32_t* emarket,
                         const int64_t* market_time_us, int64_t n_markets, int32_t n_sources,
                         const int64_t* poffsets, const int32_t* psid, const double* prel, const double* pconf,

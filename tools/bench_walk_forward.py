@@ -22,12 +22,20 @@ resolved with a random outcome, market times one hour apart.
       plan and walk on the same batch: the build, the bce_walk_lag_queries launch alone, and the
       whole walk_forward call.  Written to measurements/walk_lag.txt.
 
+  (g) ``--scoped-lag``, in place of (a)-(e): the NAMESPACED walk with resolution lag
+      (WalkScopePlan.build_lagged) on the same batches, 3 domains assigned at random, against the
+      ordinary namespaced plan and walk: the build (``resolve == forecast`` and a lag of 0 to 72
+      hours), the whole walk_forward_scoped call, and a K = 6 walk_sweep_scoped against six
+      separate walk_forward_scoped(commit=False) + score calls.  Written to
+      measurements/walk_scope_lag.txt.
+
 Every timing is ``--calls`` back-to-back calls between two device synchronises on the host
 clock, each call that writes the table preceded by a reset from a pristine copy; the variants run
 interleaved, ``--reps`` times each.  All (b) variants must give identical tables.
 
     python tools/bench_walk_forward.py [--signals N] [--sources S] [--out measurements/walk_forward.txt]
     python tools/bench_walk_forward.py --lag [--out measurements/walk_lag.txt]
+    python tools/bench_walk_forward.py --scoped-lag [--out measurements/walk_scope_lag.txt]
 """
 from __future__ import annotations
 
@@ -220,6 +228,118 @@ def run_lag(name, off_h, sid_h, S, args, say):
     return same_plan and same_table and all(x[2] for x in launches)
 
 
+def run_scoped_lag(name, off_h, sid_h, S, args, say):
+    """(g): WalkScopePlan.build_lagged / walk_forward_scoped / walk_sweep_scoped against the ordinary ones."""
+    dev = torch.device("cuda", 0)
+    D = 3
+    outcome_h, prob_h = outcomes_and_probs(off_h, sid_h, S, seed=17)
+    M, Nsig = len(off_h) - 1, len(sid_h)
+    rng = np.random.default_rng(29)
+    md_h = rng.integers(0, D, M).astype(np.int32)
+    off, sid, prob, outcome, md = (torch.from_numpy(x).to(dev) for x in (off_h, sid_h, prob_h, outcome_h, md_h))
+    forecast_h = T0 + HOUR * np.arange(M, dtype=np.int64)
+    lag_h = HOUR * np.random.default_rng(23).integers(0, 73, M)
+    forecast, drawn = torch.from_numpy(forecast_h).to(dev), torch.from_numpy(forecast_h + lag_h).to(dev)
+    calls = args.calls
+    common = (off, sid, prob, outcome, md, S, D)
+    builds = [("WalkScopePlan.build", lambda: batch.WalkScopePlan.build(*common, update_global=True)),
+              ("build_lagged, resolve == forecast",
+               lambda: batch.WalkScopePlan.build_lagged(*common, forecast, forecast, update_global=True)),
+              ("build_lagged, lag 0..72 h",
+               lambda: batch.WalkScopePlan.build_lagged(*common, forecast, drawn, update_global=True))]
+    plain, zero, lagged = [run() for _, run in builds]  # warm-up: code objects, torch sort workspaces
+    E, F = plain.pairs.n_entries, plain.dplan.n_entries
+    moved = [int((getattr(lagged, q).qlast != getattr(plain, q).qlast).sum()) for q in ("dq", "gq")]
+    say(f"== {name}: {M} markets, {Nsig} signals, {S} sources, {D} domains at random; {E} entries, {F} (domain, "
+        f"source) chains; {calls} calls per timing; the drawn lag moves qlast of {moved[0]} domain and {moved[1]} "
+        f"global queries")
+    same_plan = all(torch.equal(getattr(getattr(zero, q), k), getattr(getattr(plain, q), k))
+                    for q in ("dq", "gq") for k in ("qstart", "qpos", "qentry", "qlast", "slast")) and \
+        all(torch.equal(getattr(zero, sp).bits, getattr(plain, sp).bits) for sp in ("dsettle", "gsettle"))
+    say(f"resolve == forecast gives the ordinary plan's arrays: {same_plan}")
+    times = {label: [] for label, _ in builds}
+    for _ in range(max(args.reps, 3)):
+        for label, run in builds:
+            times[label].append(timed(run)[0])
+    for label, _ in builds:
+        say(f"(g) {label:<52} ms: {fmt(times[label])}   (min {min(times[label]) * 1e3:.3f})")
+    bins = batch.Plan.build_device(off)
+    table = Table(S, dev)
+    names = [""] * S
+    d, s = np.nonzero(rng.random((D, S)) < 0.5)  # a row for half of the (domain, source) pairs, a fifth without a stamp
+    has = (rng.random(len(d)) < 0.8).astype(np.uint8)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    stamps = np.where(has, 1_700_000_000_000_000, N.NO_TIMESTAMP).astype(np.int64)
+    domains = batch.PairTable.from_rows(T(d.astype(np.int64)), T(s.astype(np.int32)), T(rng.random(len(d))),
+                                        T(rng.random(len(d))), T(stamps), T(has), D, S)
+
+    def rt():
+        return batch.ReliabilityTable(*table.live, names)
+
+    def whole(p, *mt):
+        def run():
+            out = None
+            for _ in range(calls):
+                table.reset()
+                out = batch.walk_forward_scoped(p, domains, rt(), *mt, offsets=off, prob=prob, bins=bins,
+                                                validate=False)
+            return out
+        return run
+
+    hl, mr = [30.0, 5.0, 90.0], [0.1, 0.4]
+
+    def sweep(p, *mt):
+        def run():
+            for _ in range(calls):
+                batch.walk_sweep_scoped(p, domains, rt(), *mt, offsets=off, prob=prob, half_life_days=hl, min_rel=mr,
+                                        bins=bins, validate=False)
+        return run
+
+    def six(p, *mt):
+        def run():
+            for _ in range(calls):
+                for _ in range(len(hl) * len(mr)):
+                    res = batch.walk_forward_scoped(p, domains, rt(), *mt, offsets=off, prob=prob, bins=bins,
+                                                    validate=False, commit=False)
+                    batch.score_markets(res, off, outcome)
+        return run
+
+    variants = [("walk_forward_scoped, ordinary plan", whole(plain, forecast)),
+                ("walk_forward_scoped, lagged plan, resolve == forecast", whole(zero)),
+                ("walk_forward_scoped, lagged plan, lag 0..72 h", whole(lagged)),
+                ("walk_sweep_scoped K = 6, ordinary plan", sweep(plain, forecast)),
+                ("six walk_forward_scoped(commit=False) + score, ordinary", six(plain, forecast)),
+                ("walk_sweep_scoped K = 6, lagged plan, lag 0..72 h", sweep(lagged)),
+                ("six walk_forward_scoped(commit=False) + score, lagged", six(lagged))]
+    snaps = []
+    for label, run in variants[:2]:  # warm-up and the result check
+        res = run()
+        torch.cuda.synchronize()
+        snaps.append((table.snapshot(), res))
+    same_walk = same(snaps[0][0], snaps[1][0]) and \
+        snaps[0][1].consensus.view(torch.int64).equal(snaps[1][1].consensus.view(torch.int64)) and \
+        snaps[0][1].scope.equal(snaps[1][1].scope) and \
+        all(torch.equal(getattr(snaps[0][1].domains, f), getattr(snaps[1][1].domains, f))
+            for f in ("poffsets", "psid", "rel", "conf", "t_us", "has"))
+    say(f"the ordinary walk and the lagged one with resolve == forecast agree in every consensus, scope, domain row "
+        f"and global row: {same_walk}")
+    for label, run in variants[2:]:
+        run()
+    table.reset()
+    N.check_faults(dev, "bench walk scope lag")
+    times = {label: [] for label, _ in variants}
+    for _ in range(max(args.reps, 3)):
+        for label, run in variants:
+            times[label].append(timed(run)[0] / calls)
+    for label, _ in variants:
+        say(f"(g) {label:<56} ms/call: {fmt(times[label])}   (min {min(times[label]) * 1e3:.3f})")
+    mn = {label: min(t) for label, t in times.items()}
+    say(f"lagged (resolve == forecast) / ordinary whole call by minima: "
+        f"{mn[variants[1][0]] / mn[variants[0][0]]:.3f}x; six separate / sweep by minima: ordinary "
+        f"{mn[variants[4][0]] / mn[variants[3][0]]:.2f}x, lagged {mn[variants[6][0]] / mn[variants[5][0]]:.2f}x")
+    return same_plan and same_walk
+
+
 def run_slice(off_h, sid_h, prob_h, outcome_h, S, args, say):
     """(e): the first --slice-markets markets, the per-market loop against one walk_forward."""
     dev = torch.device("cuda", 0)
@@ -287,10 +407,17 @@ def main() -> int:
     ap.add_argument("--chunk-bits", type=int, nargs="+", default=[64, 256, 1024])
     ap.add_argument("--shapes", default="c3,uniform")
     ap.add_argument("--lag", action="store_true", help="(f): the walk with resolution lag, in place of (a)-(e)")
-    ap.add_argument("--out", default=None, help="default: measurements/walk_forward.txt (--lag: walk_lag.txt)")
+    ap.add_argument("--scoped-lag", action="store_true",
+                    help="(g): the namespaced walk with resolution lag and its sweep, in place of (a)-(e)")
+    ap.add_argument("--out", default=None,
+                    help="default: measurements/walk_forward.txt (--lag: walk_lag.txt, --scoped-lag: "
+                         "walk_scope_lag.txt)")
     args = ap.parse_args()
+    if args.lag and args.scoped_lag:
+        ap.error("--lag and --scoped-lag are two runs")
     if args.out is None:
-        args.out = os.path.join(ROOT, "measurements", "walk_lag.txt" if args.lag else "walk_forward.txt")
+        args.out = os.path.join(ROOT, "measurements", "walk_scope_lag.txt" if args.scoped_lag else
+                                "walk_lag.txt" if args.lag else "walk_forward.txt")
     N.require_gpu()  # a measurement without a GPU fails; there is nothing else to time
     lines = []
 
@@ -303,11 +430,12 @@ def main() -> int:
     off_h, sid_h, _, _ = make_c3_full(total=args.signals, S=args.sources)
     ok = True
     for shape in args.shapes.split(","):
-        if args.lag and shape in ("c3", "uniform"):
+        if (args.lag or args.scoped_lag) and shape in ("c3", "uniform"):
             src = sid_h
             if shape == "uniform":
                 src = np.random.default_rng(71).integers(0, args.sources, len(sid_h)).astype(np.int32)
-            ok = run_lag("c3 (Zipf 1.1 sources)" if shape == "c3" else "uniform sources", off_h, src, args.sources,
+            run = run_scoped_lag if args.scoped_lag else run_lag
+            ok = run("c3 (Zipf 1.1 sources)" if shape == "c3" else "uniform sources", off_h, src, args.sources,
                          args, say) and ok
         elif shape == "c3":
             ok = run_shape("c3 (Zipf 1.1 sources)", off_h, sid_h, args.sources, args, say)[0] and ok
