@@ -12,7 +12,7 @@ Layout (include/bce.h):
 
 Every name lives in one submodule and is re-exported here; a submodule imports only from those
 listed before it: elementwise, tables, consensus, tiebreak, stats, reestimate_csr, settle, pairs,
-walk, glob, score.
+walk, glob, score, history.
 """
 from .elementwise import (DECAY_HALF_LIFE_DAYS, DECAY_MINIMUM, DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY, decay_apply,
                           decay_view, outcome_update, pack_flags2, replay_step)
@@ -38,3 +38,5 @@ from .glob import (_GLOB_ANY, _GLOB_CLS, _GLOB_LIT, _GLOB_NEGATE, _GLOB_STAR, GL
 from .score import (SCORE_COUNTS, SCORE_LANES, SCORE_MAX_BINS, SCORE_SEG, SCORE_SUMS, ScorePlan, ScoreResult,
                     _nan_div, _score_segments, score, score_markets, score_sources, walk_sweep,
                     walk_sweep_scoped)
+from .history import (HISTORY_MAX_LEN, HistoryResult, _history_items, _market_of_point, consensus_history, history_at,
+                      score_history, walk_history)

@@ -114,6 +114,31 @@ class Market:
         self.consensus_result = result
         return result
 
+    def consensus_history(self, source_reliability: Optional[Dict[str, Dict[str, float]]] = None
+                          ) -> List[Dict[str, Any]]:
+        """The consensus after every signal arrived, in one launch (``batch.consensus_history``):
+        entry k is ``{"signals": k + 1, "sourceId": that of signal k, "consensus": a float or None,
+        "confidence", "totalWeight", "sourceCount"}``, equal to the corresponding fields of
+        ``compute_consensus(self.signals[:k + 1], source_reliability)`` -- what calling
+        ``add_signal`` and ``compute_consensus`` in turn would have returned (market.py:104-115).
+        An empty market gives ``[]``; ``consensus_result`` is not touched."""
+        if not self.signals:
+            return []
+        rel = source_reliability or {}
+        ids = sorted({s["sourceId"] for s in self.signals})  # core.py:103
+        rank = {sid: i for i, sid in enumerate(ids)}
+        off, sid, prob = signals_csr([self.signals], rank)
+        rows = [rel.get(i, {}) for i in ids]  # core.py:110-112
+        N.require_gpu()
+        T = batch.to_device(N.device())
+        table = batch.SourceTable.from_arrays(
+            T(np.array([float(r.get("reliability", DEFAULT_RELIABILITY)) for r in rows], np.float64)),
+            T(np.array([float(r.get("confidence", DEFAULT_CONFIDENCE)) for r in rows], np.float64)),
+            T(np.array([i in rel for i in ids], np.uint8)), ids)
+        h = batch.consensus_history(T(off), T(sid), T(prob), table, offsets_host=off, check=True)
+        return _history_rows(self.signals, *(x.cpu().numpy() for x in (h.consensus, h.confidence, h.total_weight,
+                                                                       h.n_unique)))
+
     def resolve(self, outcome: bool) -> None:
         self.outcome = outcome
         self.status = MarketStatus.RESOLVED
@@ -221,6 +246,17 @@ class MarketStore:
                 results[key] = res
         return results
 
+    def compute_all_history(self, reliability_store: Optional[SQLiteReliabilityStore] = None
+                            ) -> Dict[str, List[Dict[str, Any]]]:
+        """``Market.consensus_history`` for all open markets in ONE batched launch: market id ->
+        the list of its entries (``[]`` for a market without signals).  The table is the one
+        ``compute_all_consensus`` reads: with a store, every (source, market) pair fetched and
+        decayed at "now" (market.py:208-219).  No market's ``consensus_result`` is touched."""
+        markets = self.list_markets(status=MarketStatus.OPEN)
+        busy = [m for m in markets if m.signals]
+        computed = _batched_history(busy, reliability_store) if busy else {}
+        return {str(m.id): computed.get(str(m.id), []) for m in markets}
+
 
 def _domain_fn(domain_of):
     """``domain_of=``: a callable ``Market -> Optional[str]``, or "category" (MarketId.category)."""
@@ -239,8 +275,11 @@ class _FirstSeen(dict):
         return rank
 
 
-def _batched_consensus(markets: List[Market], store: Optional[SQLiteReliabilityStore]) -> Dict[str, Dict[str, Any]]:
-    """CSR over the markets, ranks over (market position, sorted sourceId)."""
+def _batched_table(markets: List[Market], store: Optional[SQLiteReliabilityStore]):
+    """The batch ``_batched_consensus`` and ``_batched_history`` run on: CSR over the markets, ranks
+    over (market position, sorted sourceId), and the consensus table over those ranks -- with a
+    store, every (source, market) pair fetched and decayed at "now".  Returns ``(per_market_ids,
+    off, (offsets, sid, prob) on the device, table)``."""
     per_market_ids: List[List[str]] = []
     key_names: List[str] = []
 
@@ -274,8 +313,34 @@ def _batched_consensus(markets: List[Market], store: Optional[SQLiteReliabilityS
         table = rt.consensus_table(dt_to_us(_decay.datetime.now(timezone.utc)))
     else:
         table = batch.SourceTable.from_arrays(T(rel[:S]), T(conf[:S]), T(present[:S]), key_names)
-    res = batch.consensus(T(off), T(sid), T(prob), table, validate=False, check=True)
+    return per_market_ids, off, (T(off), T(sid), T(prob)), table
+
+
+def _batched_consensus(markets: List[Market], store: Optional[SQLiteReliabilityStore]) -> Dict[str, Dict[str, Any]]:
+    """One consensus launch over the batch of :func:`_batched_table`."""
+    per_market_ids, off, csr, table = _batched_table(markets, store)
+    res = batch.consensus(*csr, table, validate=False, check=True)
     return _render_markets(markets, per_market_ids, off, res)
+
+
+def _history_rows(signals, cons, confd, tot, nu) -> List[Dict[str, Any]]:
+    """``Market.consensus_history``'s entries from one market's slices of a HistoryResult."""
+    rows = []
+    for k, s in enumerate(signals):
+        null = tot[k] == 0  # core.py:131
+        rows.append({"signals": k + 1, "sourceId": s["sourceId"], "consensus": None if null else float(cons[k]),
+                     "confidence": 0.0 if null else float(confd[k]), "totalWeight": float(tot[k]),
+                     "sourceCount": int(nu[k])})
+    return rows
+
+
+def _batched_history(markets: List[Market], store: Optional[SQLiteReliabilityStore]) -> Dict[str, List[Dict[str, Any]]]:
+    """One history launch (``batch.consensus_history``) over the batch of :func:`_batched_table`."""
+    _, off, csr, table = _batched_table(markets, store)
+    h = batch.consensus_history(*csr, table, offsets_host=off, check=True)
+    cons, confd, tot, nu = (x.cpu().numpy() for x in (h.consensus, h.confidence, h.total_weight, h.n_unique))
+    return {str(m.id): _history_rows(m.signals, cons[a:b], confd[a:b], tot[a:b], nu[a:b])
+            for m, a, b in zip(markets, off[:-1], off[1:])}
 
 
 def _render_markets(markets: List[Market], per_market_ids, offsets, res) -> Dict[str, Dict[str, Any]]:

@@ -3,8 +3,9 @@
 // kernels; consensus_lane.hip: the lane-per-market kernels for n <= 32, their shared pieces in
 // consensus_lane.hpp; consensus_tab.hip: the LDS-table kernel for contiguous short markets;
 // consensus_wide.hip: 64 < n <= 4096, its sort network in wide_sort.hpp and its chain loops in
-// ordered_chain.hpp; consensus_api.hip: the C entries that pick among them; plan.hip: the
-// planners), and the few device pieces every one of them writes the same way.
+// ordered_chain.hpp; consensus_history.hip: every market's consensus after each signal;
+// consensus_api.hip: the C entries that pick among them; plan.hip: the planners), and the few
+// device pieces every one of them writes the same way.
 #pragma once
 #pragma clang fp contract(off)
 

@@ -199,6 +199,41 @@ int bce_consensus_planned(const int64_t* offsets, int64_t n_markets, const int32
                           int32_t* n_unique, int32_t* err_idx, int32_t* usid, double* weight,
                           double* nweight, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ---- consensus history: every market's consensus after each signal arrived --------
+ *
+ * Replaces: the online use of a Market (market.py: add_signal, compute_consensus, add_signal
+ * again): point k of market m, stored at CSR position offsets[m] + k, is
+ * core.compute_consensus (core.py:63-180) of the market's first k + 1 signals in arrival
+ * (CSR) order.  Per point: consensus (0.0 where the reference returns None, core.py:131-133),
+ * confidence (0.0 there too), total_weight, n_unique; null <=> total_weight == 0.  All four
+ * outputs have n_signals elements.  Probabilities outside [0, 1] are computed, not rejected
+ * (bce_validate_csr is the range check).  Exact order only; no per-unique outputs.
+ *
+ * Every signal is read once (the expansion into prefix markets reads (n + 1) / 2 times as
+ * many); the arithmetic is quadratic in a market's length by construction (each prefix is
+ * its own ordered sum).  Markets of up to 4096 signals; a longer one (or one longer than a
+ * max_len <= 64 launch takes) is left untouched and raises the device fault word, as does a
+ * sid outside [0, n_sources), whose row read is clamped (bce_fault_check).  present_bits is
+ * not read (cold sources carry their defaults in relconf) and may be NULL.
+ *
+ * Which markets, and how they are launched:
+ *   bin_start_host and bin_start_dev NULL: markets market_list[0..n_list) (NULL: all) in ONE
+ *     launch sized by max_len, an upper bound on their lengths (0 = unknown: as 4096); no host
+ *     synchronisation.
+ *   bin_start_host (host int64[BCE_NBINS+1], bce_plan_bins / bce_plan_bins_device): market_list
+ *     is the plan's order (device); one launch per non-empty length bin, longest first.
+ *   bin_start_dev (device int64[BCE_NBINS+1], bce_plan_bins_device_async): the same with the
+ *     bin boundaries read on the device; no host synchronisation.
+ * Positions of markets outside the list or the plan are left untouched.  A NULL required
+ * pointer, a negative size or max_len outside [0, 4096] returns BCE_EINVAL before anything
+ * touches the GPU. */
+int bce_consensus_history(const int64_t* offsets, int64_t n_markets, const int32_t* sid, const double* prob,
+                          int64_t n_signals, const double* relconf, const uint32_t* present_bits,
+                          int32_t n_sources, const int32_t* market_list, int64_t n_list,
+                          const int64_t* bin_start_host, const int64_t* bin_start_dev, int32_t max_len,
+                          double* consensus, double* confidence, double* total_weight, int32_t* n_unique,
+                          void* stream);
+
 /* ---- decay: get_reliability(apply_decay=True) over a table ----------------------
  * Replaces: decay.apply_reliability_decay (decay.py:61-100) composed with
  * decay.days_since_update (decay.py:103-145) as used by
