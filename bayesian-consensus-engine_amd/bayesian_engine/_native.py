@@ -24,6 +24,7 @@ MODE_FAST = 1
 NBINS = 13  # include/bce.h BCE_NBINS
 PAIR_STORE, PAIR_NAMESPACED, PAIR_RAW = 0, 1, 2  # include/bce.h bce_pair_mode
 SCORE_MAX_BINS, SCORE_SEG, SCORE_LANES = 32, 2048, 256  # include/bce.h BCE_SCORE_*
+BOOT_MAX_SETS, BOOT_TILE = 8, 256  # include/bce.h BCE_BOOT_*
 NO_TIMESTAMP = -(2**63)
 TB_LABELS = {0: "unanimous", 1: "weight_density", 2: "prediction_value_smallest", 3: "unanimous"}
 
@@ -126,6 +127,10 @@ _SIGS = {
     "bce_score_scratch_bytes": (_i64, [_i64, _i32]),
     "bce_score_groups": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _f64,
                                    _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bce_boot_weights_host": (C.c_int, [_i64, _vp, _i64, _vp, _i64, _vp]),
+    "bce_boot_scratch_bytes": (_i64, [_i64, _i64, _i32]),
+    "bce_score_bootstrap": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i64,
+                                      _vp, _vp, _i64, _f64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -23,6 +23,7 @@ reference's semantics.
 from __future__ import annotations
 
 import fnmatch
+import math
 from dataclasses import dataclass, field
 from datetime import datetime, timezone
 from enum import Enum
@@ -36,7 +37,7 @@ from . import batch
 from .config import DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY
 from .core import compute_consensus, consensus_dict, signals_csr
 from .reliability import SQLiteReliabilityStore
-from .reliability_abstraction import NamespacedReliabilityStore
+from .reliability_abstraction import NamespacedReliabilityStore, _check_boot
 from . import decay as _decay
 from .timeutil import NO_TIMESTAMP, dt_to_us, iso_to_us, us_to_iso
 
@@ -481,6 +482,93 @@ class WalkScore:
     sources: Dict[str, SourceScore]
 
 
+@dataclass
+class DecayRow:
+    """One grid point of a :class:`DecayComparison`: ``n`` scored markets, the point estimate
+    ``value`` of the metric with its percentile interval ``[lo, hi]``, the paired difference
+    ``diff`` against the reference point (this point minus the reference, under the same
+    resamples) with ``[diff_lo, diff_hi]``, ``p_better`` = the share of replicates in which this
+    point is strictly better than the reference, ``p_best`` = the share in which it is the best
+    of the grid.  None where nothing was scored."""
+
+    params: Dict[str, float]
+    n: int
+    value: Optional[float]
+    lo: Optional[float]
+    hi: Optional[float]
+    diff: Optional[float]
+    diff_lo: Optional[float]
+    diff_hi: Optional[float]
+    p_better: Optional[float]
+    p_best: Optional[float]
+
+
+@dataclass
+class DecayComparison:
+    """``CrossMarketAggregator.compare_decay``: one :class:`DecayRow` per grid point (row-major,
+    ``min_rel`` fastest), ``best`` = the index of the best point estimate (None where nothing was
+    scored) and ``reference`` = the index every ``diff`` / ``p_better`` is taken against."""
+
+    rows: List[DecayRow]
+    best: Optional[int]
+    reference: Optional[int]
+    metric: str
+    level: float
+    n_boot: int
+    seed: int
+    block: int
+
+
+COMPARE_METRICS = ("brier", "log_loss", "accuracy", "skill")
+
+
+def _compare_arguments(what, store, half_life_days, min_rel, n_boot, block, metric, level, reference):
+    """The checked arguments of a decay comparison: ``(half_life_days, min_rel)``."""
+    hl, mr, _ = _sweep_arguments(what, store, half_life_days, min_rel, 10)
+    _check_boot(n_boot, block)
+    if isinstance(reference, bool) or not (reference is None or isinstance(reference, (int, np.integer))):
+        raise TypeError(f"reference must be a grid index or None (got {type(reference).__name__})")
+    if reference is not None and not 0 <= reference < len(hl) * len(mr):
+        raise ValueError(f"reference must be a grid index in [0, {len(hl) * len(mr)}) (got {reference})")
+    if metric not in COMPARE_METRICS:
+        raise ValueError(f"metric must be one of {COMPARE_METRICS} (got {metric!r})")
+    if metric == "skill":
+        raise ValueError("metric 'skill' needs a base forecast: a decay comparison has none")
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError(f"level must be in (0, 1) (got {level})")
+    return hl, mr
+
+
+def _comparison(run, hl, mr, metric, level, reference, n_boot, seed, block) -> "DecayComparison":
+    """The :class:`DecayComparison` of a store's ``(scores, boot)`` (None: no signals)."""
+    params = [{"half_life_days": h, "min_rel": m} for h in hl for m in mr]
+    level = float(level)
+    if run is None:
+        rows = [DecayRow(p, 0, None, None, None, None, None, None, None, None) for p in params]
+        return DecayComparison(rows, None, reference, metric, level, n_boot, seed, block)
+    _, boot = run
+    point = boot.point(metric)[0].cpu().numpy()
+    n = boot.W[0, 0].cpu().numpy()
+    finite = ~np.isnan(point)
+    best = None
+    if finite.any():
+        key = np.where(finite, -point if metric == "accuracy" else point, np.inf)
+        best = int(np.argmin(key))  # the first of equal point estimates
+    ref = best if reference is None else int(reference)
+    lo, hi = (x[0].cpu().numpy() for x in boot.interval(metric, level))
+    p_best = boot.p_best(metric)[0].cpu().numpy()
+    none = [None] * len(params)
+    d = d_lo = d_hi = p_better = none
+    if ref is not None:
+        dd, dl, dh = boot.diff(metric, ref, level)
+        d, d_lo, d_hi = dd[0, 0].cpu().numpy(), dl[0].cpu().numpy(), dh[0].cpu().numpy()
+        p_better = boot.p_better(metric, ref)[0].cpu().numpy()
+    val = lambda x, k: None if x[k] is None or math.isnan(float(x[k])) else float(x[k])  # noqa: E731
+    rows = [DecayRow(p, int(n[k]), val(point, k), val(lo, k), val(hi, k), val(d, k), val(d_lo, k), val(d_hi, k),
+                     val(p_better, k), val(p_best, k)) for k, p in enumerate(params)]
+    return DecayComparison(rows, best, ref, metric, level, n_boot, seed, block)
+
+
 def _keyed_results(keyed, results) -> Dict[str, Dict[str, Any]]:
     """The result dicts of a walk keyed by ``str(market.id)``, in walk order."""
     out = {}
@@ -891,6 +979,43 @@ class CrossMarketAggregator:
         scores = store.sweep_decay_namespaced(batch_markets, stamps, hl, mr, n_bins=B, resolve_times=resolve_stamps,
                                               **kw)
         return _sweep_rows(scores, hl, mr, B)
+
+    def compare_decay(self, store, half_life_days, min_rel, patterns: Optional[List[str]] = None,
+                      domain: Optional[str] = None, lagged: bool = False, device_match: Optional[bool] = None,
+                      n_boot: int = 1000, seed: int = 0, block: int = 1, metric: str = "brier", level: float = 0.95,
+                      reference: Optional[int] = None) -> "DecayComparison":
+        """:meth:`sweep_decay` with the question a sweep leaves open: is the best grid point
+        better than the others, or is the difference noise?  The same walk and sweep, then a
+        paired Poisson bootstrap over the markets on the GPU (``store.compare_decay``,
+        ``batch.score_bootstrap``): every grid point is re-scored under the same ``n_boot``
+        resamples (``seed``; ``block`` consecutive markets of the walk are resampled together, for
+        a history whose neighbours depend on each other).  Returns a :class:`DecayComparison` for
+        ``metric`` ("brier", "log_loss" or "accuracy"): per grid point the estimate with its
+        ``level`` percentile interval, the paired difference against ``reference`` (a grid index;
+        default: the point with the best estimate) with its interval, and the shares of
+        replicates in which the point beats the reference / is the best of the grid."""
+        hl, mr = _compare_arguments("compare_decay", store, half_life_days, min_rel, n_boot, block, metric, level,
+                                    reference)
+        _, batch_markets, stamps, resolve_stamps = self._walk_history(patterns, device_match, lagged)
+        run = store.compare_decay(batch_markets, stamps, hl, mr, domain=domain, resolve_times=resolve_stamps,
+                                  n_boot=n_boot, seed=seed, block=block)
+        return _comparison(run, hl, mr, metric, level, reference, n_boot, seed, block)
+
+    def compare_decay_namespaced(self, store, half_life_days, min_rel, domain_of,
+                                 patterns: Optional[List[str]] = None, update_global: bool = False,
+                                 market_scope: bool = False, lagged: bool = False,
+                                 device_match: Optional[bool] = None, n_boot: int = 1000, seed: int = 0,
+                                 block: int = 1, metric: str = "brier", level: float = 0.95,
+                                 reference: Optional[int] = None) -> "DecayComparison":
+        """:meth:`compare_decay` over the namespaced walk (the arguments of
+        :meth:`sweep_decay_namespaced`, then those of :meth:`compare_decay`)."""
+        hl, mr = _compare_arguments("compare_decay_namespaced", store, half_life_days, min_rel, n_boot, block,
+                                    metric, level, reference)
+        _, batch_markets, stamps, resolve_stamps, kw = self._namespaced_history(
+            domain_of, patterns, update_global, market_scope, lagged, device_match)
+        run = store.compare_decay_namespaced(batch_markets, stamps, hl, mr, resolve_times=resolve_stamps,
+                                             n_boot=n_boot, seed=seed, block=block, **kw)
+        return _comparison(run, hl, mr, metric, level, reference, n_boot, seed, block)
 
     def summarize_category(self, category: str) -> Dict[str, Any]:
         markets = self._store.list_markets(pattern=f"{category}:*")

@@ -157,6 +157,15 @@ _SCOPE_NS = {batch.NS_MARKET: (ReliabilityNamespace.MARKET, False),
              batch.NS_GLOBAL: (ReliabilityNamespace.GLOBAL, True)}
 
 
+def _check_boot(n_boot, block) -> None:
+    """The bootstrap arguments of the ``compare_decay`` methods."""
+    for name, x in (("n_boot", n_boot), ("block", block)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise TypeError(f"{name} must be an int (got {type(x).__name__})")
+        if x < 1:
+            raise ValueError(f"{name} must be >= 1 (got {x})")
+
+
 class NamespacedReliabilityStore:
     """Reliability store with namespace-aware fallback chain (reliability_abstraction.py:84-291).
 
@@ -462,6 +471,16 @@ class NamespacedReliabilityStore:
         :class:`batch.ScoreResult` of the whole history with a leading grid dimension
         ``[len(half_life_days) * len(min_rel), 1, ...]`` (``min_rel`` fastest), or None for a
         history without signals.  ``resolve_times`` as :meth:`walk_forward`."""
+        run = self._sweep_run(markets, times, half_life_days, min_rel, domain, n_bins, resolve_times, False,
+                              "sweep_decay")
+        return None if run is None else run[0]
+
+    def _sweep_run(self, markets, times, half_life_days, min_rel, domain, n_bins, resolve_times, keep_consensus,
+                   what):
+        """What :meth:`sweep_decay` and :meth:`compare_decay` share: the compiled plan and
+        :func:`batch.walk_sweep`.  ``(scores, kept, outcome)`` with ``kept`` the ``[K, M]``
+        consensus and null mask (``keep_consensus``) and ``outcome`` the int8[M] device tensor;
+        None for a history without signals."""
         markets = [(list(signals), outcome) for signals, outcome in markets]
         t_us, r_us = _walk_times_us(markets, times, resolve_times)
         _, _, target = self._update_scope(domain)
@@ -474,12 +493,41 @@ class NamespacedReliabilityStore:
         dev = N.device()
         T = batch.to_device(dev)
         off, prob = T(offsets), T(prob)
-        plan, mtime = _walk_plan(off, T(sid), prob, T(_outcome_codes(markets)), len(names), t_us, r_us, T)
+        outcome = T(_outcome_codes(markets))
+        plan, mtime = _walk_plan(off, T(sid), prob, outcome, len(names), t_us, r_us, T)
         table = self._store.load_table(target, names, device=dev)
-        scores, _ = batch.walk_sweep(plan, table, mtime, offsets=off, prob=prob, half_life_days=half_life_days,
-                                     min_rel=min_rel, n_bins=n_bins)
-        N.check_faults(dev, "sweep_decay")
-        return scores
+        scores, kept = batch.walk_sweep(plan, table, mtime, offsets=off, prob=prob, half_life_days=half_life_days,
+                                        min_rel=min_rel, n_bins=n_bins, keep_consensus=keep_consensus)
+        N.check_faults(dev, what)
+        return scores, kept, outcome
+
+    @staticmethod
+    def _compare(scores, kept, outcome, n_boot, seed, block, what):
+        """The bootstrap of a sweep's kept consensus: one group of all markets, one set per grid
+        point, ``unit = market // block``."""
+        cons, nulls = kept
+        M = outcome.numel()
+        dev = cons.device
+        boot = batch.score_bootstrap(batch.ScorePlan.whole(M, device=dev), cons, outcome, valid=~nulls,
+                                     unit=batch.boot_units(M, block, device=dev), n_boot=n_boot, seed=seed)
+        N.check_faults(dev, what)
+        return scores, boot
+
+    def compare_decay(self, markets: Sequence[tuple], times: Sequence, half_life_days: Sequence[float],
+                      min_rel: Sequence[float], domain: Optional[str] = None,
+                      resolve_times: Optional[Sequence] = None, n_boot: int = 1000, seed: int = 0, block: int = 1):
+        """:meth:`sweep_decay` with a paired bootstrap over the markets: is the difference between
+        two grid points more than noise?  The same plan and the same :func:`batch.walk_sweep`
+        (``keep_consensus=True``), then :func:`batch.score_bootstrap` over one group of all
+        markets with one forecast set per grid point, every set under the same ``n_boot``
+        resamples (``seed``; ``block`` consecutive markets of the walk are resampled together).
+        Nothing is written.  Returns ``(scores, boot)``: the :class:`batch.ScoreResult` of
+        :meth:`sweep_decay` and a :class:`batch.BootstrapResult` ``[n_boot + 1, 1, K, ...]``, or
+        None for a history without signals."""
+        _check_boot(n_boot, block)
+        run = self._sweep_run(markets, times, half_life_days, min_rel, domain, 10, resolve_times, True,
+                              "compare_decay")
+        return None if run is None else self._compare(*run, n_boot, seed, block, "compare_decay")
 
     def _namespaced_walk(self, markets, times, domains, market_ids, update_global, resolve_times):
         """What :meth:`walk_forward_namespaced` and :meth:`sweep_decay_namespaced` share: the
@@ -603,14 +651,34 @@ class NamespacedReliabilityStore:
         is written.  Returns the :class:`batch.ScoreResult` of the whole history with a leading
         grid dimension ``[len(half_life_days) * len(min_rel), 1, ...]`` (``min_rel`` fastest), or
         None for a history without signals.  ``resolve_times`` as :meth:`walk_forward_namespaced`."""
+        run = self._sweep_run_namespaced(markets, times, half_life_days, min_rel, domains, market_ids, update_global,
+                                         n_bins, resolve_times, False, "sweep_decay_namespaced")
+        return None if run is None else run[0]
+
+    def _sweep_run_namespaced(self, markets, times, half_life_days, min_rel, domains, market_ids, update_global,
+                              n_bins, resolve_times, keep_consensus, what):
+        """:meth:`_sweep_run` over the namespaced walk."""
         _, _, b = self._namespaced_walk(markets, times, domains, market_ids, update_global, resolve_times)
         if b is None:
             return None
-        scores, _ = batch.walk_sweep_scoped(b["plan"], b["dtable"], b["gtable"], b["mtime"], offsets=b["off"],
-                                            prob=b["prob"], half_life_days=half_life_days, min_rel=min_rel,
-                                            pairs=b["ptable"], global_has=b["ghas"], n_bins=n_bins)
-        N.check_faults(b["dev"], "sweep_decay_namespaced")
-        return scores
+        scores, kept = batch.walk_sweep_scoped(b["plan"], b["dtable"], b["gtable"], b["mtime"], offsets=b["off"],
+                                               prob=b["prob"], half_life_days=half_life_days, min_rel=min_rel,
+                                               pairs=b["ptable"], global_has=b["ghas"], n_bins=n_bins,
+                                               keep_consensus=keep_consensus)
+        N.check_faults(b["dev"], what)
+        return scores, kept, b["plan"].outcome
+
+    def compare_decay_namespaced(self, markets: Sequence[tuple], times: Sequence, half_life_days: Sequence[float],
+                                 min_rel: Sequence[float], domains=None, market_ids: Optional[Sequence[str]] = None,
+                                 update_global: bool = False, resolve_times: Optional[Sequence] = None,
+                                 n_boot: int = 1000, seed: int = 0, block: int = 1):
+        """:meth:`compare_decay` over the namespaced walk: the plan and sweep of
+        :meth:`sweep_decay_namespaced`, then the same paired bootstrap.  Returns ``(scores,
+        boot)`` or None for a history without signals."""
+        _check_boot(n_boot, block)
+        run = self._sweep_run_namespaced(markets, times, half_life_days, min_rel, domains, market_ids, update_global,
+                                         10, resolve_times, True, "compare_decay_namespaced")
+        return None if run is None else self._compare(*run, n_boot, seed, block, "compare_decay_namespaced")
 
     def get_reliability_many(self, names: Sequence[str], market_id: Optional[str] = None,
                              domain: Optional[str] = None, apply_decay: bool = True,

@@ -22,13 +22,12 @@
 #include "bce_device.hpp"
 #include "bce_internal.hpp"
 #include "consensus_common.hpp"
+#include "score_item.hpp"
 
 #pragma clang fp contract(off)
 
 namespace bce {
 
-constexpr int kScoreT = 256;
-constexpr int kScoreSeg = BCE_SCORE_SEG;
 constexpr int kScorePer = kScoreSeg / kScoreT;  // items per lane and segment
 static_assert(kScoreSeg % kScoreT == 0, "a segment is a whole number of lane strides");
 
@@ -58,13 +57,6 @@ struct ScoreArgs {
   int* fault;
 };
 
-enum { kScScored = 0, kScHit = 1, kScUnresolved = 2, kScNull = 3, kScBad = 4 };
-
-// The segments a group of `len` items is cut into (an empty group keeps one, which writes zeros).
-__host__ __device__ inline int64_t score_segments(int64_t len) {
-  return len <= 0 ? 1 : (len + kScoreSeg - 1) / kScoreSeg;
-}
-
 // Fold the 256 lane partials of column c by the halving tree; valid in lane 0 of the wave.
 __device__ __forceinline__ double score_tree(const double* col, int lane) {
   double v0 = col[lane], v1 = col[lane + 64];
@@ -83,22 +75,8 @@ __global__ __launch_bounds__(kScoreT) void score_segment_kernel(ScoreArgs a) {
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int B = a.B;
   const int64_t seg = blockIdx.x;
-  const int64_t g = a.seg_group[seg];  // one load: a search of seg_start costs ~20 dependent ones
-  int code = 0;
-  int64_t i0 = 0, i1 = 0;  // the segment's items
-  int64_t j = -1;
-  if (g >= 0 && g < a.G && seg < a.seg_start[g + 1]) j = seg - a.seg_start[g];
-  if (j < 0) {
-    code = kFaultOffsets;  // the segment table is no partition: the row is zeros
-  } else {
-    const int64_t b = a.goff[g], e = a.goff[g + 1];
-    if (b < 0 || e < b || e > a.n_items) {
-      code = kFaultOffsets;  // the group reads as empty
-    } else if (j < score_segments(e - b)) {
-      i0 = b + j * kScoreSeg;
-      i1 = i0 + kScoreSeg < e ? i0 + kScoreSeg : e;
-    }
-  }
+  int64_t i0, i1;  // the segment's items
+  int code = score_segment_items(a.goff, a.G, a.seg_start, a.seg_group, a.n_items, seg, &i0, &i1);
   for (int c = t; c < 5 + 2 * B; c += kScoreT) sInt[c] = 0;
   for (int b = 0; b < B; ++b) sCol[(3 + b) * kScoreT + t] = 0.0;
   __syncthreads();
@@ -131,27 +109,14 @@ __global__ __launch_bounds__(kScoreT) void score_segment_kernel(ScoreArgs a) {
 #pragma unroll
   for (int k = 0; k < kScorePer; ++k) {
     if (cls[k] < 0) continue;
-    if (cls[k] == 0) {
-      if (o[k] < 0) cls[k] = kScUnresolved;
-      else if (!ok[k]) cls[k] = kScNull;
-      else if (!(v[k] >= 0.0 && v[k] <= 1.0) || (a.base && !(bs[k] >= 0.0 && bs[k] <= 1.0))) cls[k] = kScBad;
-      else cls[k] = kScScored;
-    }
+    if (cls[k] == 0) cls[k] = score_class(v[k], o[k], ok[k], a.base != nullptr, bs[k]);
     atomicAdd(&sInt[cls[k]], 1);
     if (cls[k] != kScScored) continue;
-    const double od = (double)o[k];
-    const double d = v[k] - od;
-    const double dd = d * d;
-    brier = brier + dd;
-    const double q = o[k] ? v[k] : 1.0 - v[k];
-    const double lt = -log(q < a.eps ? a.eps : q);
-    ll = ll + lt;
-    if (a.base) {
-      const double db = bs[k] - od;
-      const double dbb = db * db;
-      bbase = bbase + dbb;
-    }
-    if ((v[k] >= 0.5) == (o[k] == 1)) atomicAdd(&sInt[kScHit], 1);  // market.py:298-301
+    const ScoreTerms it = score_terms(v[k], o[k], a.base != nullptr, bs[k], a.eps);
+    brier = brier + it.brier;
+    ll = ll + it.logloss;
+    if (a.base) bbase = bbase + it.brier_base;
+    if (it.hit) atomicAdd(&sInt[kScHit], 1);
     int bin = (int)(v[k] * (double)B);
     if (bin > B - 1) bin = B - 1;
     atomicAdd(&sInt[5 + bin], 1);

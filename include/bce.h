@@ -804,6 +804,67 @@ int bce_score_groups(const int64_t* group_offsets, int64_t n_groups, const int64
                      int64_t scratch_bytes, int64_t* counts, double* sums, int64_t* bin_n,
                      int64_t* bin_pos, double* bin_psum, void* stream);
 
+/* ---- bootstrap of the back-test scores: intervals and paired comparisons -----------------------
+ * Is 0.2013 against 0.2017 a difference or noise?  A paired Poisson bootstrap over markets: the
+ * sums of bce_score_groups under n_rep resamples of the history, for n_sets forecast sets (the
+ * grid points of a sweep) that all see the SAME resample, so the per-replicate difference of two
+ * sets is a paired difference.  No index gather: replicate r gives the unit u the integer weight
+ *   mix(z):  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *            z ^= z >> 31                                       (uint64, wrapping: splitmix64)
+ *   GOLD   = 0x9E3779B97F4A7C15
+ *   key(r) = mix(seed + (uint64)r * GOLD)
+ *   h(r,u) = mix(key(r) ^ mix((uint64)u + GOLD))
+ *   w(r,u) = 1                                 for r == 0 (the sample itself)
+ *          = #{k in 0..20 : h(r,u) >= T[k]}    for r >= 1
+ *   T[k]   = min(floor(2^64 * sum_{j<=k} e^-1 / j!), 2^64 - 1)   (csrc/boot_weights.hpp: 21
+ *            constants, T[0] = 0x5e2d58d8b3bcdf1a ... T[20] = 0xffffffffffffffff)
+ * so w is Poisson(1) in 0..21 and no floating point enters the sampler.  seed is a uint64 passed
+ * as the int64 of the same bit pattern.  u is the resampling unit of the item's market m =
+ * oidx[i]: unit[m] (int64[n_markets], any value, hashed as its bit pattern), or m itself when
+ * unit is NULL.  unit = m / block is a block bootstrap, any id array a cluster bootstrap; with a
+ * per-source plan all signals of a market share its weight.
+ *
+ * bce_boot_weights_host: w[R][U] = w(replicates[i], units[u]) over HOST arrays, no GPU; a negative
+ *   replicate returns BCE_EINVAL.
+ * bce_score_bootstrap: groups, segment table, items and markets as bce_score_groups.  Set k reads
+ *   value[k * value_stride + pidx[i]] and valid[k * valid_stride + m] (valid nullable;
+ *   valid_stride 0: one mask for all sets); outcome, base and unit are shared.  Classes and
+ *   per-item terms are exactly those of bce_score_groups, per set (csrc/score_item.hpp: one copy);
+ *   only scored items contribute: W += w, W_hit += w where the item is a hit, and each sum adds
+ *   (double)w * term, the product and then the add (no contraction).  Replicate rep0 + j is row j:
+ *   counts int64[n_rep][G][n_sets][2] = {W, W_hit}, sums fp64[n_rep][G][n_sets][3] = {brier,
+ *   logloss, brier_base}.  An infinite term (eps = 0) under w = 0 gives NaN, as the product does.
+ *
+ * REDUCTION SHAPE (every output depends on the arguments alone -- not on the grid, the tiling,
+ * rep0, n_sets, n_rep or the other groups of the call; no floating-point atomics):
+ *   1. a group is cut into segments of BCE_SCORE_SEG consecutive items as in bce_score_groups;
+ *   2. inside a segment, the terms w * term of its items are added left to right from 0.0 (an
+ *      item that is not scored contributes 0.0);
+ *   3. the group's sum is 0.0 + segment 0 + segment 1 + ..., left to right.
+ * Integers are plain sums.  (Row 0 therefore holds the same counts as bce_score_groups, and sums
+ * that differ from its sums by the summation order only.)
+ *
+ * scratch: device buffer of bce_boot_scratch_bytes(n_segments, n_rep, n_sets) bytes, 8-byte
+ * aligned (one row per segment, replicate and set); the function returns 0 for arguments out of
+ * range.  The kernel stages BCE_BOOT_TILE items of a segment at a time.  Nothing synchronises.
+ * Bad arguments (a negative size or stride, n_sets outside [1, BCE_BOOT_MAX_SETS], rep0 < 0,
+ * eps < 0 or NaN, a NULL required pointer, a short or misaligned scratch) return BCE_EINVAL before
+ * anything touches the GPU.  On the device, broken offsets, segment tables and indices behave as
+ * in bce_score_groups: the item or group contributes nothing and the device fault word is raised
+ * (bce_fault_check); nothing is read or written outside the arrays. */
+#define BCE_BOOT_MAX_SETS 8
+#define BCE_BOOT_TILE 256 /* items staged at a time */
+int bce_boot_weights_host(int64_t seed, const int64_t* replicates, int64_t R, const int64_t* units, int64_t U,
+                          int32_t* w);
+int64_t bce_boot_scratch_bytes(int64_t n_segments, int64_t n_rep, int32_t n_sets);
+int bce_score_bootstrap(const int64_t* group_offsets, int64_t n_groups, const int64_t* seg_start,
+                        const int64_t* seg_group, int64_t n_segments, const int64_t* pidx, const int64_t* oidx,
+                        int64_t n_items, const double* value, int64_t n_values, int64_t value_stride,
+                        int32_t n_sets, const int8_t* outcome, const uint8_t* valid, int64_t valid_stride,
+                        const double* base, const int64_t* unit, int64_t n_markets, double eps, int64_t seed,
+                        int64_t rep0, int64_t n_rep, void* scratch, int64_t scratch_bytes, int64_t* counts,
+                        double* sums, void* stream);
+
 /* ---- JSONL front end (host C++, no GPU): SURVEY §8 f2 -----------------------------------
  *
  * Replaces, for a batch: cli._cmd_consensus_legacy / _cmd_consensus (cli.py:25-52,163-174)
