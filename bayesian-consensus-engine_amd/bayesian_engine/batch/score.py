@@ -8,7 +8,7 @@ from .. import _native as N
 from .tables import ReliabilityTable, SourceTable, _check_csr, _entry_buffers
 from .consensus import Plan, _alloc, consensus
 from .pairs import _bins_as_plan
-from .walk import (WalkPlan, WalkScopePlan, _walk_read, _walk_scope_launch, _walk_scope_traces,
+from .walk import (WalkPlan, WalkScopePlan, _check_batch, _walk_read, _walk_scope_launch, _walk_scope_traces,
                    _walk_settle_trace)
 
 SCORE_SEG = N.SCORE_SEG          # items of a segment (include/bce.h BCE_SCORE_SEG)
@@ -279,23 +279,34 @@ def score_sources(plan: ScorePlan, prob: torch.Tensor, outcome: torch.Tensor,
     return score(plan, prob.to(torch.float64), outcome, valid=valid, base=consensus, **kw)
 
 
-def _sweep_grid(half_life_days: Sequence[float], min_rel: Sequence[float], what: str):
-    """The grid of a sweep as two lists of floats; an empty axis is a ``ValueError``."""
-    hl, mr = [float(x) for x in half_life_days], [float(x) for x in min_rel]
-    if not hl or not mr:
+def _sweep_setup(plan, offsets: torch.Tensor, prob: torch.Tensor, half_life_days: Sequence[float],
+                 min_rel: Sequence[float], what: str, dev):
+    """What :func:`walk_sweep` and :func:`walk_sweep_scoped` open with: ``(grid, trace, read
+    buffers)`` -- the grid as two lists of floats (an empty axis is a ``ValueError``), the checks
+    that ``plan`` keeps its outcomes and fits the batch, a trace buffer [E, 2] and the
+    :func:`_entry_buffers` every grid point is read into."""
+    grid = [float(x) for x in half_life_days], [float(x) for x in min_rel]
+    if not grid[0] or not grid[1]:
         raise ValueError(f"{what} needs at least one half_life_days and one min_rel")
-    return hl, mr
+    if plan.outcome is None:
+        kind = type(plan).__name__
+        raise ValueError(f"{what} needs a {kind} from {kind}.build (it keeps the outcomes)")
+    _check_batch(plan, offsets, prob)
+    E = plan.pairs.n_entries
+    return grid, _entry_buffers(E, dev)[0], _entry_buffers(E, dev)
 
 
-def _sweep(pairs, outcome: torch.Tensor, read, wtable: SourceTable, offsets: torch.Tensor, prob: torch.Tensor, hl, mr,
+def _sweep(plan, read, relconf: torch.Tensor, bits: torch.Tensor, offsets: torch.Tensor, prob: torch.Tensor, grid,
            score_plan: Optional[ScorePlan], keep_consensus: bool, mode: str, n_bins: int, eps: float,
            consensus_kwargs: dict):
     """The grid loop of :func:`walk_sweep` and :func:`walk_sweep_scoped`: for every point,
-    ``read(half_life_days, min_rel)`` fills ``wtable`` (the consensus table over the entries of
-    ``pairs``), then :func:`consensus` and :func:`score` against ``outcome``.  The length-bin
-    plan, the consensus outputs and the scoring scratch are allocated once."""
+    ``read(half_life_days, min_rel)`` fills ``relconf`` / ``bits`` (the consensus table over the
+    entries of ``plan``), then :func:`consensus` and :func:`score` against the plan's outcomes.
+    The length-bin plan, the consensus outputs and the scoring scratch are allocated once."""
+    pairs, outcome, (hl, mr) = plan.pairs, plan.outcome, grid
     M, E = pairs.n_markets, pairs.n_entries
-    dev = wtable.relconf.device
+    wtable = SourceTable(relconf, bits, range(E))
+    dev = relconf.device
     if score_plan is None:
         score_plan = ScorePlan.whole(M, device=dev)
     prob = prob.to(torch.float64)
@@ -342,23 +353,15 @@ def walk_sweep(plan: WalkPlan, table: "ReliabilityTable", market_time_us: Option
     ``[len(half_life_days) * len(min_rel), G, ...]`` over ``score_plan`` (default: one group of all
     markets) and, with ``keep_consensus``, the fp64 ``[K, M]`` consensus and bool ``[K, M]``
     null mask of every point (else None)."""
-    pp = plan.pairs
-    hl, mr = _sweep_grid(half_life_days, min_rel, "walk_sweep")
-    if plan.outcome is None:
-        raise ValueError("walk_sweep needs a WalkPlan from WalkPlan.build (it keeps the outcomes)")
-    if offsets.numel() - 1 != pp.n_markets or prob.numel() != pp.esid.numel():
-        raise ValueError("offsets / prob are not the batch the plan was built from")
-    E = pp.n_entries
-    dev = table.rel.device
-    trace, _, _ = _entry_buffers(E, dev)
-    relconf, bits, exists = _entry_buffers(E, dev)
+    grid, trace, (relconf, bits, exists) = _sweep_setup(plan, offsets, prob, half_life_days, min_rel, "walk_sweep",
+                                                        table.rel.device)
     _walk_settle_trace(plan, table, market_time_us, trace, long_min, chunk_bits)
 
     def read(h, m):
         _walk_read(plan, table, market_time_us, trace, relconf, bits, exists, all_present, h, m)
 
-    return _sweep(pp, plan.outcome, read, SourceTable(relconf, bits, range(E)), offsets, prob, hl, mr, score_plan,
-                  keep_consensus, mode, n_bins, eps, consensus_kwargs)
+    return _sweep(plan, read, relconf, bits, offsets, prob, grid, score_plan, keep_consensus, mode, n_bins, eps,
+                  consensus_kwargs)
 
 
 def walk_sweep_scoped(plan: WalkScopePlan, domains: "PairTable", global_table: Optional["ReliabilityTable"],
@@ -377,21 +380,13 @@ def walk_sweep_scoped(plan: WalkScopePlan, domains: "PairTable", global_table: O
     overwrite the global trace in place; here the traces must outlive the read), then
     :func:`consensus` and :func:`score`.  No input is written.  The arguments are those of
     :func:`walk_forward_scoped` and :func:`walk_sweep`; returns what :func:`walk_sweep` returns."""
-    pp = plan.pairs
-    hl, mr = _sweep_grid(half_life_days, min_rel, "walk_sweep_scoped")
-    if plan.outcome is None:
-        raise ValueError("walk_sweep_scoped needs a WalkScopePlan from WalkScopePlan.build (it keeps the outcomes)")
-    if offsets.numel() - 1 != pp.n_markets or prob.numel() != pp.esid.numel():
-        raise ValueError("offsets / prob are not the batch the plan was built from")
-    E = pp.n_entries
-    dev = pp.esid.device
-    gtrace, _, _ = _entry_buffers(E, dev)
-    relconf, bits, scope = _entry_buffers(E, dev)
+    grid, gtrace, (relconf, bits, scope) = _sweep_setup(plan, offsets, prob, half_life_days, min_rel,
+                                                        "walk_sweep_scoped", plan.pairs.esid.device)
     tr = _walk_scope_traces(plan, domains, global_table, market_time_us, pairs, global_has, long_min, chunk_bits,
                             gtrace)
 
     def read(h, m):
         _walk_scope_launch(plan, tr, global_table, market_time_us, pairs, mark_cold, h, m, relconf, bits, scope)
 
-    return _sweep(pp, plan.outcome, read, SourceTable(relconf, bits, range(E)), offsets, prob, hl, mr, score_plan,
-                  keep_consensus, mode, n_bins, eps, consensus_kwargs)
+    return _sweep(plan, read, relconf, bits, offsets, prob, grid, score_plan, keep_consensus, mode, n_bins, eps,
+                  consensus_kwargs)

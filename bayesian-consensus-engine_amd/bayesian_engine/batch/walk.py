@@ -42,6 +42,21 @@ def _entry_signals(pairs: PairPlan) -> torch.Tensor:
     return torch.bincount(pairs.esid.to(torch.int64), minlength=E)[:E]
 
 
+def _query_order(chain: torch.Tensor, n_chains: int, partial: bool = False):
+    """The queries of a chain family in (chain, market) order (torch only, any device): ``(qstart
+    int64[n_chains + 1], qentry int64[Q], skey int64[Q])``, ``skey`` the chain of every query.
+    ``chain`` int64[E] is the chain of every entry (entries ascend by market); ``partial``: the
+    entries with ``chain < 0`` are no queries."""
+    sel = None
+    if partial:
+        sel = torch.nonzero(chain >= 0).flatten()
+        chain = chain[sel]
+    skey, qentry = torch.sort(chain, stable=True)  # entries ascend by market: (chain, market) order
+    qstart = torch.zeros(n_chains + 1, dtype=torch.int64, device=chain.device)
+    qstart[1:] = torch.cumsum(torch.bincount(chain, minlength=n_chains), 0)
+    return qstart, (qentry if sel is None else sel[qentry]), skey
+
+
 def _chain_queries(chain: torch.Tensor, cnt: torch.Tensor, emarket: torch.Tensor, n_chains: int,
                    partial: bool = False):
     """:func:`_walk_queries` for any family of chains over the entries (torch only, any device):
@@ -53,15 +68,8 @@ def _chain_queries(chain: torch.Tensor, cnt: torch.Tensor, emarket: torch.Tensor
     E, C = chain.numel(), int(n_chains)
     dev = chain.device
     i64 = dict(dtype=torch.int64, device=dev)
-    if partial:
-        sel = torch.nonzero(chain >= 0).flatten()
-        chain = chain[sel]
-    skey, qentry = torch.sort(chain, stable=True)  # entries ascend by market: (chain, market) order
+    qstart, qentry, skey = _query_order(chain, C, partial)
     Q = qentry.numel()
-    qstart = torch.zeros(C + 1, **i64)
-    qstart[1:] = torch.cumsum(torch.bincount(chain, minlength=C), 0)
-    if partial:
-        qentry = sel[qentry]
     c = cnt[qentry]
     excl = torch.cumsum(c, 0) - c
     first = qstart[skey]                       # the chain's first query
@@ -98,15 +106,45 @@ class WalkQueries:
     slast: torch.Tensor
 
 
+class _WalkPlanBase:
+    """What :class:`WalkPlan` and :class:`WalkScopePlan` share.  Each ends in ``outcome`` (int8[M]
+    as given to build: scoring reads it) and, from build_lagged, ``forecast_time_us`` /
+    ``resolve_time_us`` int64[M] (the latter read where ``outcome >= 0``)."""
+
+    @property
+    def lagged(self) -> bool:
+        return self.forecast_time_us is not None
+
+    @staticmethod
+    def _checked(offsets, sid, outcome, n_sources, times):
+        """The argument checks of a compile, ``times`` its ``(forecast, resolve)`` times or None,
+        then ``(S, sid clamped into [0, S), how many were outside)`` (torch only, any device)."""
+        M, _, S, _, _ = _check_csr(offsets, sid, n_sources, outcome=outcome, values=False)
+        if times is not None:
+            _check_lag_times(*times, outcome, M)
+        clamped = sid.to(torch.int32).clamp(0, S - 1)
+        return S, clamped, int((clamped != sid).sum())
+
+    @staticmethod
+    def _compiled(what: str, check: bool, lagged: bool, n_clamped: int, n_sources: int, device) -> None:
+        """The tail of a checked compile: the fault word of the lag-query launches, then the
+        clamped sids (the settlement compile sees one only in a market that feeds a chain)."""
+        if check and lagged:
+            N.check_faults(device, f"{what} lag queries")
+        if check and n_clamped:
+            raise N.BCEError(f"{what} plan: {n_clamped} sid outside [0, {int(n_sources)})")
+
+
 @dataclass
-class WalkPlan:
+class WalkPlan(_WalkPlanBase):
     """A chronological CSR batch compiled for :func:`walk_forward`: the :class:`SettlePlan` of its
     resolved markets, the :class:`PairPlan` entry list over ALL markets, and one query per entry,
-    regrouped by source: ``qstart`` int64[S+1], ``qpos`` int64[E] (query order, ascending inside a
-    source: the chain position whose before-state the query reads, 0 <= qpos <= chain length),
-    ``qentry`` int32[E] (the entry a query answers), ``qlast`` int32[E] (by entry: the market of
-    chain bit ``qpos - 1``, -1 when ``qpos == 0``) and ``slast`` int64[S] (the last resolved
-    market of every source, -1 where none).  ``n_clamped``: sids outside ``[0, n_sources)``.
+    regrouped by source (together: ``queries``): ``qstart`` int64[S+1], ``qpos`` int64[E] (query
+    order, ascending inside a source: the chain position whose before-state the query reads, 0 <=
+    qpos <= chain length), ``qentry`` int32[E] (the entry a query answers), ``qlast`` int32[E] (by
+    entry: the market of chain bit ``qpos - 1``, -1 when ``qpos == 0``) and ``slast`` int64[S]
+    (the last resolved market of every source, -1 where none).  ``n_clamped``: sids outside ``[0,
+    n_sources)``.
 
     A plan from :meth:`build_lagged` (``lagged``) carries a forecast and a resolve time per market
     (DESIGN §4.21): its chains are in (resolve time, market, position) order, ``qpos`` counts the
@@ -121,13 +159,9 @@ class WalkPlan:
     qlast: torch.Tensor
     slast: torch.Tensor
     n_clamped: int
-    outcome: Optional[torch.Tensor] = None  # int8[M], as given to build (scoring reads it)
-    forecast_time_us: Optional[torch.Tensor] = None  # int64[M], build_lagged only
-    resolve_time_us: Optional[torch.Tensor] = None   # int64[M], read where outcome >= 0
-
-    @property
-    def lagged(self) -> bool:
-        return self.forecast_time_us is not None
+    outcome: Optional[torch.Tensor] = None
+    forecast_time_us: Optional[torch.Tensor] = None
+    resolve_time_us: Optional[torch.Tensor] = None
 
     @property
     def total(self) -> torch.Tensor:
@@ -146,11 +180,26 @@ class WalkPlan:
               n_sources: int):
         """The integer half of :meth:`build` (torch only, CPU tensors included): ``(pairs, qstart,
         qpos, qentry, qlast, slast, n_clamped)``.  Argument errors as :meth:`SettlePlan.build`."""
-        S = _check_csr(offsets, sid, n_sources, outcome=outcome, values=False)[2]
-        clamped = sid.to(torch.int32).clamp(0, S - 1)
-        n_clamped = int((clamped != sid).sum())
+        S, clamped, n_clamped = cls._checked(offsets, sid, outcome, n_sources, None)
         pairs = PairPlan.build(offsets, clamped, prob, S)  # checks offsets / prob
         return (pairs, *_walk_queries(pairs, offsets, outcome), n_clamped)
+
+    @classmethod
+    def _compile(cls, offsets, sid, prob, outcome, n_sources, check, times=None):
+        """:meth:`build` and, with the ``(forecast, resolve)`` times, :meth:`build_lagged`."""
+        S, clamped, n_clamped = cls._checked(offsets, sid, outcome, n_sources, times)
+        pairs = PairPlan.build(offsets, clamped, prob, S)  # checks offsets / prob
+        if times is None:
+            q = WalkQueries(*_walk_queries(pairs, offsets, outcome))
+            splan = SettlePlan.build(offsets, sid, prob, outcome, n_sources, check=check)
+        else:
+            times = forecast, resolve = times[0].contiguous(), times[1].contiguous()
+            N.require_gpu()
+            splan, q = _lag_family(offsets, sid, prob, outcome, n_sources, check, _resolve_rank(outcome, resolve),
+                                   pairs, pairs.usid, forecast, resolve)
+        cls._compiled("walk", check, times is not None, n_clamped, n_sources, offsets.device)
+        return cls(splan, pairs, q.qstart, q.qpos, q.qentry, q.qlast, q.slast, n_clamped, outcome.contiguous(),
+                   *(times or ()))
 
     @classmethod
     def build(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
@@ -159,11 +208,7 @@ class WalkPlan:
         int8[M] (-1 unresolved, 0, 1).  Torch sorts and scans plus :meth:`SettlePlan.build`;
         synchronises.  A ``sid`` outside ``[0, n_sources)`` is clamped and raises
         :class:`BCEError` (``check=False``: the fault is left for :func:`walk_forward`)."""
-        pairs, qstart, qpos, qentry, qlast, slast, n_clamped = cls.order(offsets, sid, prob, outcome, n_sources)
-        splan = SettlePlan.build(offsets, sid, prob, outcome, n_sources, check=check)
-        if check and n_clamped:  # in an unresolved market: the settlement compile does not see it
-            raise N.BCEError(f"walk plan: {n_clamped} sid outside [0, {int(n_sources)})")
-        return cls(splan, pairs, qstart, qpos, qentry, qlast, slast, n_clamped, outcome.contiguous())
+        return cls._compile(offsets, sid, prob, outcome, n_sources, check)
 
     @classmethod
     def build_lagged(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
@@ -182,22 +227,7 @@ class WalkPlan:
         in (source, market) order as in :meth:`build`, and one launch of bce_walk_lag_queries
         bisects every query's visible prefix.  With ``resolve == forecast`` the plan equals
         :meth:`build`'s, array for array."""
-        M, _, S, _, _ = _check_csr(offsets, sid, n_sources, outcome=outcome, values=False)
-        _check_lag_times(forecast_time_us, resolve_time_us, outcome, M)
-        clamped = sid.to(torch.int32).clamp(0, S - 1)
-        n_clamped = int((clamped != sid).sum())
-        pairs = PairPlan.build(offsets, clamped, prob, S)  # checks offsets / prob
-        forecast = forecast_time_us.contiguous()
-        resolve = resolve_time_us.contiguous()
-        N.require_gpu()
-        splan, q = _lag_family(offsets, sid, prob, outcome, n_sources, check, _resolve_rank(outcome, resolve), pairs,
-                               pairs.usid, forecast, resolve)
-        if check:
-            N.check_faults(offsets.device, "walk lag queries")
-            if n_clamped:  # in an unresolved market: the settlement compile does not see it
-                raise N.BCEError(f"walk plan: {n_clamped} sid outside [0, {int(n_sources)})")
-        return cls(splan, pairs, q.qstart, q.qpos, q.qentry, q.qlast, q.slast, n_clamped, outcome.contiguous(),
-                   forecast, resolve)
+        return cls._compile(offsets, sid, prob, outcome, n_sources, check, (forecast_time_us, resolve_time_us))
 
 
 def _resolve_rank(outcome: torch.Tensor, resolve: torch.Tensor) -> torch.Tensor:
@@ -226,21 +256,12 @@ def _lag_family(offsets: torch.Tensor, chain_sid: torch.Tensor, prob: torch.Tens
     bit_market = market[perm].contiguous()
     E, M, C = pairs.n_entries, pairs.n_markets, splan.n_sources
     dev = offsets.device
-    i64 = dict(dtype=torch.int64, device=dev)
-    key = chain[:E].to(torch.int64)
-    if partial:
-        sel = torch.nonzero(key >= 0).flatten()
-        key = key[sel]
-    qentry = torch.sort(key, stable=True).indices  # entries ascend by market: (chain, market) order
-    if partial:
-        qentry = sel[qentry]
+    qstart, qentry, _ = _query_order(chain[:E].to(torch.int64), C, partial)
     qentry = qentry.to(torch.int32).contiguous()
     Q = qentry.numel()
-    qstart = torch.zeros(C + 1, **i64)
-    qstart[1:] = torch.cumsum(torch.bincount(key, minlength=C), 0)
-    qpos = torch.empty(Q, **i64)
+    qpos = torch.empty(Q, dtype=torch.int64, device=dev)
     qlast = torch.full((E,), -1, dtype=torch.int32, device=dev)
-    slast = torch.empty(C, **i64)
+    slast = torch.empty(C, dtype=torch.int64, device=dev)
     ent = lambda t: N.ptr(t if E else None)  # noqa: E731
     qry = lambda t: N.ptr(t if Q else None)  # noqa: E731
     N.check(L.bce_walk_lag_queries(Q, qry(qentry), ent(chain), ent(pairs.emarket), E, N.ptr(splan.start), C,
@@ -268,17 +289,25 @@ def _check_lag_times(forecast_time_us: torch.Tensor, resolve_time_us: torch.Tens
 
 
 def _walk_times(plan, market_time_us: Optional[torch.Tensor]):
-    """``(stamp, now)``: the time a market's updates are stamped with and the time it is read at
-    -- the plan's resolve and forecast times, or ``market_time_us`` twice.  ``plan``: a
-    :class:`WalkPlan` or a :class:`WalkScopePlan`."""
+    """``(stamp, now)``, both contiguous: the time a market's updates are stamped with and the
+    time it is read at -- the plan's resolve and forecast times, or ``market_time_us`` twice.
+    ``plan``: a :class:`WalkPlan` or a :class:`WalkScopePlan`."""
     if plan.lagged:
         if market_time_us is not None:
             raise ValueError("a lagged plan carries its own times: market_time_us must be None")
-        return plan.resolve_time_us, plan.forecast_time_us
+        return plan.resolve_time_us.contiguous(), plan.forecast_time_us.contiguous()
     if market_time_us is None:
         raise ValueError("market_time_us is needed: the plan has no times of its own (WalkPlan.build_lagged does)")
     _check_market_time(market_time_us, plan.pairs.n_markets)
-    return market_time_us, market_time_us
+    now = market_time_us.contiguous()
+    return now, now
+
+
+def _check_batch(plan, offsets: torch.Tensor, prob: torch.Tensor) -> None:
+    """``offsets`` / ``prob`` have the sizes of the batch ``plan`` (either kind) was built from."""
+    pp = plan.pairs
+    if offsets.numel() - 1 != pp.n_markets or prob.numel() != pp.esid.numel():
+        raise ValueError("offsets / prob are not the batch the plan was built from")
 
 
 class _ConsensusFields:
@@ -338,22 +367,19 @@ def _walk_settle_trace(plan: WalkPlan, table: "ReliabilityTable", market_time_us
 def _walk_read(plan: WalkPlan, table: "ReliabilityTable", market_time_us: Optional[torch.Tensor],
                trace: torch.Tensor, relconf: torch.Tensor, bits: torch.Tensor, exists: torch.Tensor, all_present: bool,
                half_life_days: float, min_rel: float) -> None:
-    """bce_walk_read (a lagged plan: bce_walk_read_lag) from ``trace`` into ``relconf`` (may be
-    ``trace`` itself) / ``bits`` / ``exists``."""
+    """bce_walk_read_lag (an ordinary plan: its one time array twice) from ``trace`` into
+    ``relconf`` (may be ``trace`` itself) / ``bits`` / ``exists``."""
     L = N.require_gpu()
     sp, pp = plan.settle, plan.pairs
     S, E, M = sp.n_sources, pp.n_entries, pp.n_markets
     stamp, now = _walk_times(plan, market_time_us)
     ent = lambda t: N.ptr(t if E else None)  # noqa: E731
-    if plan.lagged:
-        read, times = L.bce_walk_read_lag, (N.ptr(stamp if M else None), N.ptr(now if M else None))
-    else:
-        read, times = L.bce_walk_read, (N.ptr(now.contiguous() if M else None),)
-    N.check(read(E, ent(pp.usid), ent(pp.emarket), ent(plan.qlast), N.ptr(trace), *times, M, N.ptr(table.rel),
-                 N.ptr(table.conf), N.ptr(table.t_us), N.ptr(table.present), S, float(half_life_days), float(min_rel),
-                 DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE, int(not all_present), int(plan.n_clamped > 0),
-                 N.ptr(relconf), N.ptr(bits), N.ptr(exists), N.stream(table.rel.device)),
-            "bce_walk_read_lag" if plan.lagged else "bce_walk_read")
+    N.check(L.bce_walk_read_lag(E, ent(pp.usid), ent(pp.emarket), ent(plan.qlast), N.ptr(trace),
+                                N.ptr(stamp if M else None), N.ptr(now if M else None), M, N.ptr(table.rel),
+                                N.ptr(table.conf), N.ptr(table.t_us), N.ptr(table.present), S, float(half_life_days),
+                                float(min_rel), DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE, int(not all_present),
+                                int(plan.n_clamped > 0), N.ptr(relconf), N.ptr(bits), N.ptr(exists),
+                                N.stream(table.rel.device)), "bce_walk_read_lag")
 
 
 def walk_forward(plan: WalkPlan, table: "ReliabilityTable", market_time_us: Optional[torch.Tensor] = None, *,
@@ -381,8 +407,7 @@ def walk_forward(plan: WalkPlan, table: "ReliabilityTable", market_time_us: Opti
     resolved market; ``commit=False`` leaves it untouched.  The result does not depend on
     ``long_min`` / ``chunk_bits`` (defaults WALK_LONG_MIN / WALK_CHUNK_BITS)."""
     sp, pp = plan.settle, plan.pairs
-    if offsets.numel() - 1 != pp.n_markets or prob.numel() != pp.esid.numel():
-        raise ValueError("offsets / prob are not the batch the plan was built from")
+    _check_batch(plan, offsets, prob)
     stamp, _ = _walk_times(plan, market_time_us)
     wtable, exists = walk_trace(plan, table, market_time_us, all_present=all_present, long_min=long_min,
                                 chunk_bits=chunk_bits)
@@ -412,7 +437,7 @@ def _global_outcome(outcome: torch.Tensor, market_domain: torch.Tensor, update_g
 
 
 @dataclass
-class WalkScopePlan:
+class WalkScopePlan(_WalkPlanBase):
     """A chronological CSR batch whose markets belong to different domains, compiled for
     :func:`walk_forward_scoped`.  ``pairs``: the :class:`PairPlan` over ALL markets (entries E);
     ``dplan``: the :class:`DomainPlan` (chains F) and ``dentry`` int32[E], the domain chain of
@@ -437,21 +462,16 @@ class WalkScopePlan:
     gq: WalkQueries
     update_global: bool
     n_clamped: int
-    outcome: Optional[torch.Tensor] = None  # int8[M], as given to build (scoring reads it)
-    forecast_time_us: Optional[torch.Tensor] = None  # int64[M], build_lagged only
-    resolve_time_us: Optional[torch.Tensor] = None   # int64[M], read where outcome >= 0
-
-    @property
-    def lagged(self) -> bool:
-        return self.forecast_time_us is not None
+    outcome: Optional[torch.Tensor] = None
+    forecast_time_us: Optional[torch.Tensor] = None
+    resolve_time_us: Optional[torch.Tensor] = None
 
     @classmethod
-    def _entries(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, market_domain: torch.Tensor,
-                 S: int, n_domains: int):
-        """``(pairs, dplan, dentry int64[E], n_clamped)``: the entry list, the (domain, source)
-        chains and the chain of every entry (torch only, any device)."""
-        clamped = sid.to(torch.int32).clamp(0, S - 1)
-        n_clamped = int((clamped != sid).sum())
+    def _entries(cls, offsets, sid, prob, outcome, market_domain, n_sources, n_domains, update_global, times=None):
+        """``(pairs, dplan, dentry int64[E], domain outcome, global outcome, n_clamped)`` behind the
+        argument checks: the entry list, the (domain, source) chains, the chain of every entry and
+        the outcome as either chain family sees it (torch only, any device)."""
+        S, clamped, n_clamped = cls._checked(offsets, sid, outcome, n_sources, times)
         dplan = DomainPlan.build(offsets, clamped, market_domain, S, n_domains)  # checks market_domain / offsets
         pairs = PairPlan.build(offsets, clamped, prob, S)
         E, F = pairs.n_entries, dplan.n_entries
@@ -461,7 +481,19 @@ class WalkScopePlan:
         # the (domain, source) keys of the DomainPlan ascend: the chain of an entry by search
         fkey = dplan.emarket[:F].to(torch.int64) * S + dplan.usid[:F].to(torch.int64)
         at = torch.searchsorted(fkey, edom.clamp(min=0) * S + usid) if F else torch.zeros_like(usid)
-        return pairs, dplan, torch.where(edom >= 0, at, torch.full_like(at, -1)), n_clamped
+        dentry = torch.where(edom >= 0, at, torch.full_like(at, -1))
+        dout = torch.where(dplan.market_domain >= 0, outcome, torch.full_like(outcome, -1))
+        return pairs, dplan, dentry, dout, _global_outcome(outcome, dplan.market_domain, update_global), n_clamped
+
+    @staticmethod
+    def _queries(pairs: PairPlan, dplan: "DomainPlan", dentry: torch.Tensor, dout: torch.Tensor, gout: torch.Tensor):
+        """``(dq, gq)`` of an ordinary plan (torch only, any device)."""
+        E = pairs.n_entries
+        emarket = pairs.emarket[:E].to(torch.int64)
+        signals = _entry_signals(pairs)
+        dq = _chain_queries(dentry, signals * (dout[emarket] >= 0), emarket, max(dplan.n_entries, 1), partial=True)
+        gq = _chain_queries(pairs.usid[:E].to(torch.int64), signals * (gout[emarket] >= 0), emarket, pairs.n_sources)
+        return WalkQueries(*dq), WalkQueries(*gq)
 
     @classmethod
     def order(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
@@ -469,17 +501,32 @@ class WalkScopePlan:
         """The integer half of :meth:`build` (torch only, CPU tensors included): ``(pairs, dplan,
         dentry, dq, gq, n_clamped)``.  Argument errors as :meth:`WalkPlan.order` and
         :meth:`DomainPlan.build`."""
-        S = _check_csr(offsets, sid, n_sources, outcome=outcome, values=False)[2]
-        pairs, dplan, dentry, n_clamped = cls._entries(offsets, sid, prob, market_domain, S, n_domains)
-        E, F = pairs.n_entries, dplan.n_entries
-        usid = pairs.usid[:E].to(torch.int64)
-        emarket = pairs.emarket[:E].to(torch.int64)
-        signals = _entry_signals(pairs)
-        dq = WalkQueries(*_chain_queries(dentry, signals * (outcome[emarket] >= 0), emarket, max(F, 1),
-                                         partial=True))
-        gout = _global_outcome(outcome, dplan.market_domain, update_global)
-        gq = WalkQueries(*_chain_queries(usid, signals * (gout[emarket] >= 0), emarket, S))
-        return pairs, dplan, dentry.to(torch.int32), dq, gq, n_clamped
+        pairs, dplan, dentry, dout, gout, n_clamped = cls._entries(offsets, sid, prob, outcome, market_domain,
+                                                                   n_sources, n_domains, update_global)
+        return (pairs, dplan, dentry.to(torch.int32), *cls._queries(pairs, dplan, dentry, dout, gout), n_clamped)
+
+    @classmethod
+    def _compile(cls, offsets, sid, prob, outcome, market_domain, n_sources, n_domains, update_global, check,
+                 times=None):
+        """:meth:`build` and, with the ``(forecast, resolve)`` times, :meth:`build_lagged`."""
+        update_global = bool(update_global)
+        pairs, dplan, dentry, dout, gout, n_clamped = cls._entries(offsets, sid, prob, outcome, market_domain,
+                                                                   n_sources, n_domains, update_global, times)
+        dchains = (offsets, dplan.esid, prob, dout, max(dplan.n_entries, 1), check)
+        gchains = (offsets, sid, prob, gout, n_sources, check)
+        dentry32 = dentry.to(torch.int32).contiguous()
+        if times is None:
+            dq, gq = cls._queries(pairs, dplan, dentry, dout, gout)
+            dsettle, gsettle = SettlePlan.build(*dchains), SettlePlan.build(*gchains)
+        else:
+            times = forecast, resolve = times[0].contiguous(), times[1].contiguous()
+            rank = _resolve_rank(outcome, resolve)
+            N.require_gpu()
+            dsettle, dq = _lag_family(*dchains, rank, pairs, dentry32, forecast, resolve, partial=True)
+            gsettle, gq = _lag_family(*gchains, rank, pairs, pairs.usid, forecast, resolve)
+        cls._compiled("walk scope", check, times is not None, n_clamped, n_sources, offsets.device)
+        return cls(pairs, dplan, dentry32, dsettle, gsettle, dq, gq, update_global, n_clamped, outcome.contiguous(),
+                   *(times or ()))
 
     @classmethod
     def build(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
@@ -490,16 +537,7 @@ class WalkScopePlan:
         scans plus two :meth:`SettlePlan.build`; synchronises.  A ``sid`` outside ``[0,
         n_sources)`` is clamped and raises :class:`BCEError` (``check=False``: the fault is left
         for :func:`walk_forward_scoped`)."""
-        update_global = bool(update_global)
-        pairs, dplan, dentry, dq, gq, n_clamped = cls.order(offsets, sid, prob, outcome, market_domain, n_sources,
-                                                            n_domains, update_global)
-        masked = torch.where(dplan.market_domain >= 0, outcome, torch.full_like(outcome, -1))
-        dsettle = SettlePlan.build(offsets, dplan.esid, prob, masked, max(dplan.n_entries, 1), check=check)
-        gsettle = SettlePlan.build(offsets, sid, prob, _global_outcome(outcome, dplan.market_domain, update_global),
-                                   n_sources, check=check)
-        if check and n_clamped:  # in a market that feeds no global chain: the compile does not see it
-            raise N.BCEError(f"walk scope plan: {n_clamped} sid outside [0, {int(n_sources)})")
-        return cls(pairs, dplan, dentry, dsettle, gsettle, dq, gq, update_global, n_clamped, outcome.contiguous())
+        return cls._compile(offsets, sid, prob, outcome, market_domain, n_sources, n_domains, update_global, check)
 
     @classmethod
     def build_lagged(cls, offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, outcome: torch.Tensor,
@@ -518,26 +556,8 @@ class WalkScopePlan:
         global family over ``usid`` and the S sources, the domain family over ``dentry`` and the F
         chains, its queries only the entries with ``dentry >= 0``.  With ``resolve == forecast``
         the plan equals :meth:`build`'s, array for array."""
-        M, _, S, _, _ = _check_csr(offsets, sid, n_sources, outcome=outcome, values=False)
-        _check_lag_times(forecast_time_us, resolve_time_us, outcome, M)
-        update_global = bool(update_global)
-        pairs, dplan, dentry, n_clamped = cls._entries(offsets, sid, prob, market_domain, S, n_domains)
-        dentry = dentry.to(torch.int32).contiguous()
-        forecast = forecast_time_us.contiguous()
-        resolve = resolve_time_us.contiguous()
-        rank = _resolve_rank(outcome, resolve)
-        N.require_gpu()
-        masked = torch.where(dplan.market_domain >= 0, outcome, torch.full_like(outcome, -1))
-        dsettle, dq = _lag_family(offsets, dplan.esid, prob, masked, max(dplan.n_entries, 1), check, rank, pairs,
-                                  dentry, forecast, resolve, partial=True)
-        gsettle, gq = _lag_family(offsets, sid, prob, _global_outcome(outcome, dplan.market_domain, update_global),
-                                  n_sources, check, rank, pairs, pairs.usid, forecast, resolve)
-        if check:
-            N.check_faults(offsets.device, "walk scope lag queries")
-            if n_clamped:  # in a market that feeds no global chain: the compile does not see it
-                raise N.BCEError(f"walk scope plan: {n_clamped} sid outside [0, {int(n_sources)})")
-        return cls(pairs, dplan, dentry, dsettle, gsettle, dq, gq, update_global, n_clamped, outcome.contiguous(),
-                   forecast, resolve)
+        return cls._compile(offsets, sid, prob, outcome, market_domain, n_sources, n_domains, update_global, check,
+                            (forecast_time_us, resolve_time_us))
 
 
 @dataclass
@@ -617,29 +637,24 @@ def _walk_scope_launch(plan: WalkScopePlan, tr: _ScopeTraces, global_table: Opti
                        market_time_us: Optional[torch.Tensor], pairs: Optional[PairTable], mark_cold: bool,
                        half_life_days: float, min_rel: float, relconf: torch.Tensor, bits: torch.Tensor,
                        scope: torch.Tensor) -> None:
-    """bce_walk_scope_read (a lagged plan: bce_walk_scope_read_lag) from the traces of ``tr`` into
-    ``relconf`` (may be ``tr.gtrace`` itself) / ``bits`` / ``scope``."""
+    """bce_walk_scope_read_lag (an ordinary plan: its one time array twice) from the traces of
+    ``tr`` into ``relconf`` (may be ``tr.gtrace`` itself) / ``bits`` / ``scope``."""
     L = N.lib()
     pp, g, raw = plan.pairs, global_table, tr.raw
     S, E, M, F = pp.n_sources, pp.n_entries, pp.n_markets, plan.dplan.n_entries
     stamp, now = _walk_times(plan, market_time_us)
     ent = lambda t: N.ptr(t if E else None)  # noqa: E731
-    if plan.lagged:
-        read, name = L.bce_walk_scope_read_lag, "bce_walk_scope_read_lag"
-        times = (N.ptr(stamp if M else None), N.ptr(now if M else None))
-    else:
-        read, name, times = L.bce_walk_scope_read, "bce_walk_scope_read", (N.ptr(now.contiguous() if M else None),)
     dom = [N.ptr(x) for x in ((plan.dentry, plan.dq.qlast, tr.dtrace, raw.rel, raw.conf, raw.t_us, tr.dhas)
                               if raw is not None else (None,) * 7)]
     gtraced = tr.gtrace is not None
     glo = [N.ptr(x) for x in ((plan.gq.qlast if gtraced else None, tr.gtrace, g.rel, g.conf, g.t_us,
                                tr.global_has.contiguous()) if g is not None else (None,) * 6)]
-    N.check(read(E, ent(pp.usid), ent(pp.emarket), *times, M, S,
-                 N.ptr(pairs.poffsets if pairs is not None else None), *_pair_pointers(pairs),
-                 pairs.n_rows if pairs is not None else 0, *dom, F if raw is not None else 0, *glo,
-                 float(half_life_days), float(min_rel), DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE, int(bool(mark_cold)),
-                 int(plan.n_clamped > 0), N.ptr(relconf), N.ptr(bits), N.ptr(scope),
-                 N.stream(pp.esid.device)), name)
+    N.check(L.bce_walk_scope_read_lag(
+        E, ent(pp.usid), ent(pp.emarket), N.ptr(stamp if M else None), N.ptr(now if M else None), M, S,
+        N.ptr(pairs.poffsets if pairs is not None else None), *_pair_pointers(pairs),
+        pairs.n_rows if pairs is not None else 0, *dom, F if raw is not None else 0, *glo, float(half_life_days),
+        float(min_rel), DEFAULT_RELIABILITY, DEFAULT_CONFIDENCE, int(bool(mark_cold)), int(plan.n_clamped > 0),
+        N.ptr(relconf), N.ptr(bits), N.ptr(scope), N.stream(pp.esid.device)), "bce_walk_scope_read_lag")
 
 
 def _walk_scope_read(plan: WalkScopePlan, domains: PairTable, global_table: Optional["ReliabilityTable"],
@@ -710,8 +725,7 @@ def walk_forward_scoped(plan: WalkScopePlan, domains: PairTable, global_table: O
     start row has ``has``, and every state and every committed row is stamped with the resolve
     time of the market of its chain's last bit."""
     pp = plan.pairs
-    if offsets.numel() - 1 != pp.n_markets or prob.numel() != pp.esid.numel():
-        raise ValueError("offsets / prob are not the batch the plan was built from")
+    _check_batch(plan, offsets, prob)
     stamp, _ = _walk_times(plan, market_time_us)
     wtable, scope, raw, ghas = _walk_scope_read(plan, domains, global_table, market_time_us, pairs, global_has,
                                                 mark_cold, long_min, chunk_bits, DECAY_HALF_LIFE_DAYS, DECAY_MINIMUM)

@@ -772,16 +772,12 @@ class CrossMarketAggregator:
         if domain_of is not None:
             if domain is not None:
                 raise ValueError("domain= (one for the batch) and domain_of= (one per market) exclude each other")
-            domain_of = _domain_fn(domain_of)
+            return self.walk_forward_namespaced(store, _domain_fn(domain_of), patterns, update_global, market_scope,
+                                                dry_run=dry_run, device_match=device_match)
         keyed, batch_markets, stamps, resolve_stamps = self._walk_history(patterns, device_match, lagged)
         if lagged:
             results, summary = store.walk_forward(batch_markets, stamps, domain=domain, dry_run=dry_run,
                                                   resolve_times=resolve_stamps)
-        elif domain_of is not None:
-            results, summary = store.walk_forward_namespaced(
-                batch_markets, stamps, domains=[domain_of(m) for _, _, m, _ in keyed],
-                market_ids=[str(m.id) for _, _, m, _ in keyed] if market_scope else None,
-                update_global=update_global, dry_run=dry_run)
         else:
             results, summary = store.walk_forward(batch_markets, stamps, domain=domain, dry_run=dry_run)
         return _keyed_results(keyed, results), summary

@@ -110,12 +110,59 @@ def _walk_times_us(markets, times, resolve_times):
     return t_us, r_us
 
 
-def _walk_plan(off, sid, prob, outcome, n_sources, t_us, r_us, T):
-    """``(plan, market_time_us)`` as :func:`batch.walk_forward` takes them: a lagged plan with its
-    own times where resolve times are given."""
-    if r_us is None:
-        return batch.WalkPlan.build(off, sid, prob, outcome, n_sources), T(t_us)
-    return batch.WalkPlan.build_lagged(off, sid, prob, outcome, n_sources, T(t_us), T(r_us)), None
+def _check_market_ids(market_ids, M: int) -> None:
+    """One truthy, distinct market id per market."""
+    if len(market_ids) != M:
+        raise ValueError(f"market_ids has {len(market_ids)} entries for {M} markets")
+    if not all(market_ids):
+        raise ValueError("every market id must be truthy (a falsy one selects another scope)")
+    if len(set(market_ids)) != M:
+        raise ValueError("duplicate market id in market_ids")
+
+
+@dataclass
+class _WalkBatch:
+    """A history compiled for a walk: the interned source ``names``, the host ``offsets`` and the
+    device ``off`` / ``prob`` of its CSR batch, the ``plan`` with its ``mtime`` (None for a lagged
+    plan) and, loaded by the store, ``table`` -- the walked scope, or ``__global__`` of a
+    namespaced walk, which also has the domain names and scope keys, the domain and market-scope
+    pair tables (``ptable`` None without market ids) and ``ghas``: the global row has a stamp."""
+
+    names: list
+    offsets: np.ndarray
+    off: torch.Tensor
+    prob: torch.Tensor
+    plan: object
+    mtime: Optional[torch.Tensor]
+    table: Optional["batch.ReliabilityTable"] = None
+    dnames: Optional[list] = None
+    dkeys: Optional[list] = None
+    dtable: Optional["batch.PairTable"] = None
+    ptable: Optional["batch.PairTable"] = None
+    ghas: Optional[torch.Tensor] = None
+
+    @classmethod
+    def compile(cls, markets, t_us, r_us, market_domain=None, n_domains=0, **kw):
+        """The batch of normalised ``markets`` without its tables, None for a history without
+        signals: the sources interned in sorted() order, the CSR batch on the current device and
+        its :class:`batch.WalkPlan` -- with ``market_domain`` its :class:`batch.WalkScopePlan`
+        (``kw``: ``update_global``) -- lagged, with its own times, where ``r_us`` is given."""
+        rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
+        if not rank:
+            return None
+        offsets, sid, prob = signals_csr([signals for signals, _ in markets], rank)
+        N.require_gpu()
+        T = batch.to_device(N.device())
+        off, sid, prob, outcome = T(offsets), T(sid), T(prob), T(_outcome_codes(markets))
+        if market_domain is None:
+            kind, args = batch.WalkPlan, (off, sid, prob, outcome, len(rank))
+        else:
+            kind, args = batch.WalkScopePlan, (off, sid, prob, outcome, T(market_domain), len(rank), n_domains)
+        if r_us is None:
+            plan, mtime = kind.build(*args, **kw), T(t_us)
+        else:
+            plan, mtime = kind.build_lagged(*args, T(t_us), T(r_us), **kw), None
+        return cls(list(rank), offsets, off, prob, plan, mtime)
 
 
 def _walk_dicts(markets, offsets, names, res, pairs) -> list:
@@ -332,12 +379,7 @@ class NamespacedReliabilityStore:
                 raise ValueError(f"domains has {len(domains)} entries for {len(markets)} markets")
         if market_ids is not None:
             market_ids = list(market_ids)
-            if len(market_ids) != len(markets):
-                raise ValueError(f"market_ids has {len(market_ids)} entries for {len(markets)} markets")
-            if not all(market_ids):
-                raise ValueError("every market id must be truthy (a falsy one selects another scope)")
-            if len(set(market_ids)) != len(market_ids):
-                raise ValueError("duplicate market id in market_ids")
+            _check_market_ids(market_ids, len(markets))
         rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
         names = list(rank)
         offsets, sid, prob = signals_csr([signals for signals, _ in markets], rank, settlement=True)
@@ -433,24 +475,14 @@ class NamespacedReliabilityStore:
         not arrived when it was forecast.  ``times`` must then be in order and no resolve time
         earlier than its market's time (``ValueError``); rows written back carry the resolve time
         of their last settling market."""
-        markets = [(list(signals), outcome) for signals, outcome in markets]
-        t_us, r_us = _walk_times_us(markets, times, resolve_times)
         namespace, value, target = self._update_scope(domain)
-        rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
-        names = list(rank)
-        offsets, sid, prob = signals_csr([signals for signals, _ in markets], rank)
-        outcome = _outcome_codes(markets)
-        if not names:
+        markets, b = self._scope_walk(markets, times, target, resolve_times)
+        if b is None:
             return [core_no_signals() for _ in markets], SettleSummary({}, {}, {}, {})
-        N.require_gpu()
-        dev = N.device()
-        T = batch.to_device(dev)
-        off, prob = T(offsets), T(prob)
-        plan, mtime = _walk_plan(off, T(sid), prob, T(outcome), len(names), t_us, r_us, T)
-        table = self._store.load_table(target, names, device=dev)
-        res = table.walk_forward(plan, mtime, offsets=off, prob=prob, validate=False)
-        N.check_faults(dev, "walk_forward")
-        results = _walk_dicts(markets, offsets, names, res, plan.pairs)
+        names, plan, table = b.names, b.plan, b.table
+        res = table.walk_forward(plan, b.mtime, offsets=b.off, prob=b.prob, validate=False)
+        N.check_faults(b.off.device, "walk_forward")
+        results = _walk_dicts(markets, b.offsets, names, res, plan.pairs)
         touched = sorted(int(x) for x in plan.settle.order.cpu().numpy())
         rel, conf, stamp_us = table.rel.cpu().numpy(), table.conf.cpu().numpy(), table.t_us.cpu().numpy()
         total, correct = plan.total.cpu().numpy(), plan.correct.cpu().numpy()
@@ -471,35 +503,38 @@ class NamespacedReliabilityStore:
         :class:`batch.ScoreResult` of the whole history with a leading grid dimension
         ``[len(half_life_days) * len(min_rel), 1, ...]`` (``min_rel`` fastest), or None for a
         history without signals.  ``resolve_times`` as :meth:`walk_forward`."""
-        run = self._sweep_run(markets, times, half_life_days, min_rel, domain, n_bins, resolve_times, False,
-                              "sweep_decay")
+        b = self._scope_walk(markets, times, self._update_scope(domain)[2], resolve_times)[-1]
+        run = self._sweep_run(b, half_life_days, min_rel, n_bins, False, "sweep_decay")
         return None if run is None else run[0]
 
-    def _sweep_run(self, markets, times, half_life_days, min_rel, domain, n_bins, resolve_times, keep_consensus,
-                   what):
-        """What :meth:`sweep_decay` and :meth:`compare_decay` share: the compiled plan and
-        :func:`batch.walk_sweep`.  ``(scores, kept, outcome)`` with ``kept`` the ``[K, M]``
-        consensus and null mask (``keep_consensus``) and ``outcome`` the int8[M] device tensor;
-        None for a history without signals."""
+    def _scope_walk(self, markets, times, target, resolve_times):
+        """What :meth:`walk_forward` and the single-scope sweeps share: ``(markets, batch)`` with
+        ``markets`` normalised and ``batch`` the :class:`_WalkBatch` of the interned history, its
+        compiled :class:`batch.WalkPlan` (lagged where ``resolve_times`` is given) and the loaded
+        scope; None for a history without signals."""
         markets = [(list(signals), outcome) for signals, outcome in markets]
-        t_us, r_us = _walk_times_us(markets, times, resolve_times)
-        _, _, target = self._update_scope(domain)
-        rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
-        names = list(rank)
-        if not names:
+        b = _WalkBatch.compile(markets, *_walk_times_us(markets, times, resolve_times))
+        if b is not None:
+            b.table = self._store.load_table(target, b.names, device=b.off.device)
+        return markets, b
+
+    @staticmethod
+    def _sweep_run(b, half_life_days, min_rel, n_bins, keep_consensus, what):
+        """What the four sweep methods share: :func:`batch.walk_sweep` or, for the batch of a
+        namespaced walk, :func:`batch.walk_sweep_scoped`.  ``(scores, kept, outcome)`` with
+        ``kept`` the ``[K, M]`` consensus and null mask (``keep_consensus``) and ``outcome`` the
+        int8[M] device tensor; None for no batch (a history without signals)."""
+        if b is None:
             return None
-        offsets, sid, prob = signals_csr([signals for signals, _ in markets], rank)
-        N.require_gpu()
-        dev = N.device()
-        T = batch.to_device(dev)
-        off, prob = T(offsets), T(prob)
-        outcome = T(_outcome_codes(markets))
-        plan, mtime = _walk_plan(off, T(sid), prob, outcome, len(names), t_us, r_us, T)
-        table = self._store.load_table(target, names, device=dev)
-        scores, kept = batch.walk_sweep(plan, table, mtime, offsets=off, prob=prob, half_life_days=half_life_days,
-                                        min_rel=min_rel, n_bins=n_bins, keep_consensus=keep_consensus)
-        N.check_faults(dev, what)
-        return scores, kept, outcome
+        kw = dict(offsets=b.off, prob=b.prob, half_life_days=half_life_days, min_rel=min_rel, n_bins=n_bins,
+                  keep_consensus=keep_consensus)
+        if b.dtable is None:
+            scores, kept = batch.walk_sweep(b.plan, b.table, b.mtime, **kw)
+        else:
+            scores, kept = batch.walk_sweep_scoped(b.plan, b.dtable, b.table, b.mtime, pairs=b.ptable,
+                                                   global_has=b.ghas, **kw)
+        N.check_faults(b.off.device, what)
+        return scores, kept, b.plan.outcome
 
     @staticmethod
     def _compare(scores, kept, outcome, n_boot, seed, block, what):
@@ -525,16 +560,16 @@ class NamespacedReliabilityStore:
         :meth:`sweep_decay` and a :class:`batch.BootstrapResult` ``[n_boot + 1, 1, K, ...]``, or
         None for a history without signals."""
         _check_boot(n_boot, block)
-        run = self._sweep_run(markets, times, half_life_days, min_rel, domain, 10, resolve_times, True,
-                              "compare_decay")
+        b = self._scope_walk(markets, times, self._update_scope(domain)[2], resolve_times)[-1]
+        run = self._sweep_run(b, half_life_days, min_rel, 10, True, "compare_decay")
         return None if run is None else self._compare(*run, n_boot, seed, block, "compare_decay")
 
     def _namespaced_walk(self, markets, times, domains, market_ids, update_global, resolve_times):
         """What :meth:`walk_forward_namespaced` and :meth:`sweep_decay_namespaced` share: the
         argument checks, the interned batch, the compiled :class:`batch.WalkScopePlan` (lagged
-        where ``resolve_times`` is given) and the three loaded scopes, as a dict; None for a
-        history without signals (``markets`` / ``domains`` normalised either way, as the first
-        two items of the returned tuple)."""
+        where ``resolve_times`` is given) and the three loaded scopes, as a :class:`_WalkBatch`;
+        None for a history without signals (``markets`` / ``domains`` normalised either way, as
+        the first two items of the returned tuple)."""
         markets = [(list(signals), outcome) for signals, outcome in markets]
         M = len(markets)
         t_us, r_us = _walk_times_us(markets, times, resolve_times)
@@ -543,41 +578,22 @@ class NamespacedReliabilityStore:
             raise ValueError(f"domains has {len(domains)} entries for {M} markets")
         if market_ids is not None:
             market_ids = [str(m) for m in market_ids]
-            if len(market_ids) != M:
-                raise ValueError(f"market_ids has {len(market_ids)} entries for {M} markets")
-            if not all(market_ids):
-                raise ValueError("every market id must be truthy (a falsy one selects another scope)")
-            if len(set(market_ids)) != M:
-                raise ValueError("duplicate market id in market_ids")
-        rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
-        names = list(rank)
-        if not names:
-            return markets, domains, None
-        offsets, sid, prob = signals_csr([signals for signals, _ in markets], rank)
-        outcome = _outcome_codes(markets)
+            _check_market_ids(market_ids, M)
         dnames = list(dict.fromkeys(d for d in domains if d))
         drank = {d: i for i, d in enumerate(dnames)}
         market_domain = np.array([drank[d] if d else -1 for d in domains], np.int32)
-        N.require_gpu()
-        dev = N.device()
-        T = batch.to_device(dev)
-        off, prob = T(offsets), T(prob)
-        build = (T(sid), prob, T(outcome), T(market_domain), len(names), len(dnames))
-        if r_us is None:
-            plan, mtime = batch.WalkScopePlan.build(off, *build, update_global=update_global), T(t_us)
-        else:
-            plan, mtime = batch.WalkScopePlan.build_lagged(off, *build, T(t_us), T(r_us),
-                                                           update_global=update_global), None
-        dkeys = [f"__domain__:{d}" for d in dnames]
-        dtable = self._store.load_pair_table(dkeys, names, device=dev)
-        ptable = self._store.load_pair_table(market_ids, names, device=dev) if market_ids is not None else None
-        gtable = self._store.load_table(self.GLOBAL_MARKET_ID, names, device=dev)
+        b = _WalkBatch.compile(markets, t_us, r_us, market_domain, len(dnames), update_global=update_global)
+        if b is None:
+            return markets, domains, None
+        names, dev = b.names, b.off.device
+        b.dnames, b.dkeys = dnames, [f"__domain__:{d}" for d in dnames]
+        b.dtable = self._store.load_pair_table(b.dkeys, names, device=dev)
+        b.ptable = self._store.load_pair_table(market_ids, names, device=dev) if market_ids is not None else None
+        b.table = self._store.load_table(self.GLOBAL_MARKET_ID, names, device=dev)
         stamps = self._store.fetch_pairs([(n, self.GLOBAL_MARKET_ID) for n in names])
-        ghas = T(np.array([1 if stamps.get((n, self.GLOBAL_MARKET_ID), (0, 0, ""))[2] else 0 for n in names],
-                          np.uint8))
-        return markets, domains, dict(names=names, dnames=dnames, dkeys=dkeys, offsets=offsets, off=off, prob=prob,
-                                      plan=plan, mtime=mtime, dtable=dtable, ptable=ptable, gtable=gtable, ghas=ghas,
-                                      dev=dev)
+        b.ghas = batch.to_device(dev)(np.array([1 if stamps.get((n, self.GLOBAL_MARKET_ID), (0, 0, ""))[2] else 0
+                                                for n in names], np.uint8))
+        return markets, domains, b
 
     def walk_forward_namespaced(self, markets: Sequence[tuple], times: Sequence, domains=None,
                                 market_ids: Optional[Sequence[str]] = None, update_global: bool = False,
@@ -607,12 +623,11 @@ class NamespacedReliabilityStore:
                                                     resolve_times)
         if b is None:
             return [core_no_signals() for _ in markets], SettleSummary({}, {}, {}, {})
-        names, dnames, dkeys, offsets, off, prob, plan, dtable, gtable, dev = (
-            b[k] for k in ("names", "dnames", "dkeys", "offsets", "off", "prob", "plan", "dtable", "gtable", "dev"))
-        res = batch.walk_forward_scoped(plan, dtable, gtable, b["mtime"], offsets=off, prob=prob, pairs=b["ptable"],
-                                        global_has=b["ghas"], validate=False)
+        names, dnames, dkeys, plan, gtable, dev = b.names, b.dnames, b.dkeys, b.plan, b.table, b.off.device
+        res = batch.walk_forward_scoped(plan, b.dtable, gtable, b.mtime, offsets=b.off, prob=b.prob, pairs=b.ptable,
+                                        global_has=b.ghas, validate=False)
         N.check_faults(dev, "walk_forward_namespaced")
-        results = _walk_dicts(markets, offsets, names, res, plan.pairs)
+        results = _walk_dicts(markets, b.offsets, names, res, plan.pairs)
         records, global_records, rows = {}, {}, []
         F = plan.dplan.n_entries
         if F and plan.dsettle.n_touched:  # every touched chain has a row in the new table: read them back
@@ -651,22 +666,9 @@ class NamespacedReliabilityStore:
         is written.  Returns the :class:`batch.ScoreResult` of the whole history with a leading
         grid dimension ``[len(half_life_days) * len(min_rel), 1, ...]`` (``min_rel`` fastest), or
         None for a history without signals.  ``resolve_times`` as :meth:`walk_forward_namespaced`."""
-        run = self._sweep_run_namespaced(markets, times, half_life_days, min_rel, domains, market_ids, update_global,
-                                         n_bins, resolve_times, False, "sweep_decay_namespaced")
+        b = self._namespaced_walk(markets, times, domains, market_ids, update_global, resolve_times)[-1]
+        run = self._sweep_run(b, half_life_days, min_rel, n_bins, False, "sweep_decay_namespaced")
         return None if run is None else run[0]
-
-    def _sweep_run_namespaced(self, markets, times, half_life_days, min_rel, domains, market_ids, update_global,
-                              n_bins, resolve_times, keep_consensus, what):
-        """:meth:`_sweep_run` over the namespaced walk."""
-        _, _, b = self._namespaced_walk(markets, times, domains, market_ids, update_global, resolve_times)
-        if b is None:
-            return None
-        scores, kept = batch.walk_sweep_scoped(b["plan"], b["dtable"], b["gtable"], b["mtime"], offsets=b["off"],
-                                               prob=b["prob"], half_life_days=half_life_days, min_rel=min_rel,
-                                               pairs=b["ptable"], global_has=b["ghas"], n_bins=n_bins,
-                                               keep_consensus=keep_consensus)
-        N.check_faults(b["dev"], what)
-        return scores, kept, b["plan"].outcome
 
     def compare_decay_namespaced(self, markets: Sequence[tuple], times: Sequence, half_life_days: Sequence[float],
                                  min_rel: Sequence[float], domains=None, market_ids: Optional[Sequence[str]] = None,
@@ -676,8 +678,8 @@ class NamespacedReliabilityStore:
         :meth:`sweep_decay_namespaced`, then the same paired bootstrap.  Returns ``(scores,
         boot)`` or None for a history without signals."""
         _check_boot(n_boot, block)
-        run = self._sweep_run_namespaced(markets, times, half_life_days, min_rel, domains, market_ids, update_global,
-                                         10, resolve_times, True, "compare_decay_namespaced")
+        b = self._namespaced_walk(markets, times, domains, market_ids, update_global, resolve_times)[-1]
+        run = self._sweep_run(b, half_life_days, min_rel, 10, True, "compare_decay_namespaced")
         return None if run is None else self._compare(*run, n_boot, seed, block, "compare_decay_namespaced")
 
     def get_reliability_many(self, names: Sequence[str], market_id: Optional[str] = None,

@@ -381,19 +381,20 @@ extern "C" int bce_settle_trace(const uint64_t* bits, int64_t n_bits, const int6
   return check_launch("trace_long_kernel");
 }
 
-// bce_walk_read and bce_walk_read_lag: one kernel, the two time arrays equal without lag.
-static int walk_read_launch(int64_t n_entries, const int32_t* usid, const int32_t* emarket, const int32_t* qlast,
-                            const double* trace, const int64_t* stamp_time_us, const int64_t* market_time_us,
-                            int64_t n_markets, const double* rel, const double* conf, const int64_t* t_us,
-                            const uint8_t* present, int32_t n_sources, double half_life_days, double min_rel,
-                            double default_rel, double default_conf, int mark_cold, int sid_clamped,
-                            double* relconf, uint32_t* present_bits, uint8_t* exists, void* stream) {
+// bce_walk_read_lag holds the launch; bce_walk_read is the same with the two time arrays equal.
+extern "C" int bce_walk_read_lag(int64_t n_entries, const int32_t* usid, const int32_t* emarket,
+                                 const int32_t* qlast, const double* trace, const int64_t* stamp_time_us,
+                                 const int64_t* now_time_us, int64_t n_markets, const double* rel,
+                                 const double* conf, const int64_t* t_us, const uint8_t* present, int32_t n_sources,
+                                 double half_life_days, double min_rel, double default_rel, double default_conf,
+                                 int mark_cold, int sid_clamped, double* relconf, uint32_t* present_bits,
+                                 uint8_t* exists, void* stream) {
   BCE_REQUIRE(n_entries >= 0 && n_markets >= 0 && n_sources > 0, "walk_read: bad shape");
   BCE_REQUIRE(n_entries < (1ll << 31) && n_markets < (1ll << 31), "walk_read: n_entries or n_markets >= 2^31");
   BCE_REQUIRE(n_markets > 0 || n_entries == 0, "walk_read: entries without markets");
   if (n_entries == 0 && !sid_clamped) return BCE_OK;
   BCE_REQUIRE(n_entries == 0 ||
-                  (usid && emarket && qlast && trace && stamp_time_us && market_time_us && rel && conf && t_us),
+                  (usid && emarket && qlast && trace && stamp_time_us && now_time_us && rel && conf && t_us),
               "walk_read: NULL argument");
   BCE_REQUIRE(n_entries == 0 || (relconf && present_bits), "walk_read: NULL output");
   BCE_REQUIRE((uintptr_t)relconf % 16 == 0 && (uintptr_t)trace % 16 == 0,
@@ -405,7 +406,7 @@ static int walk_read_launch(int64_t n_entries, const int32_t* usid, const int32_
   a.qlast = qlast;
   a.trace = reinterpret_cast<const double2*>(trace);
   a.stamp = stamp_time_us;
-  a.now = market_time_us;
+  a.now = now_time_us;
   a.M = n_markets;
   a.rel = rel;
   a.conf = conf;
@@ -431,21 +432,9 @@ extern "C" int bce_walk_read(int64_t n_entries, const int32_t* usid, const int32
                              int32_t n_sources, double half_life_days, double min_rel, double default_rel,
                              double default_conf, int mark_cold, int sid_clamped, double* relconf,
                              uint32_t* present_bits, uint8_t* exists, void* stream) {
-  return walk_read_launch(n_entries, usid, emarket, qlast, trace, market_time_us, market_time_us, n_markets, rel,
-                          conf, t_us, present, n_sources, half_life_days, min_rel, default_rel, default_conf,
-                          mark_cold, sid_clamped, relconf, present_bits, exists, stream);
-}
-
-extern "C" int bce_walk_read_lag(int64_t n_entries, const int32_t* usid, const int32_t* emarket,
-                                 const int32_t* qlast, const double* trace, const int64_t* stamp_time_us,
-                                 const int64_t* now_time_us, int64_t n_markets, const double* rel,
-                                 const double* conf, const int64_t* t_us, const uint8_t* present, int32_t n_sources,
-                                 double half_life_days, double min_rel, double default_rel, double default_conf,
-                                 int mark_cold, int sid_clamped, double* relconf, uint32_t* present_bits,
-                                 uint8_t* exists, void* stream) {
-  return walk_read_launch(n_entries, usid, emarket, qlast, trace, stamp_time_us, now_time_us, n_markets, rel, conf,
-                          t_us, present, n_sources, half_life_days, min_rel, default_rel, default_conf, mark_cold,
-                          sid_clamped, relconf, present_bits, exists, stream);
+  return bce_walk_read_lag(n_entries, usid, emarket, qlast, trace, market_time_us, market_time_us, n_markets, rel,
+                           conf, t_us, present, n_sources, half_life_days, min_rel, default_rel, default_conf,
+                           mark_cold, sid_clamped, relconf, present_bits, exists, stream);
 }
 
 extern "C" int bce_walk_lag_queries(int64_t n_queries, const int32_t* qentry, const int32_t* usid,

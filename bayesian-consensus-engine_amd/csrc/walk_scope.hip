@@ -148,25 +148,26 @@ __global__ __launch_bounds__(256) void walk_scope_read_kernel(WalkScopeArgs a) {
 
 using namespace bce;
 
-// bce_walk_scope_read and bce_walk_scope_read_lag: one kernel, the two time arrays equal without lag.
-static int walk_scope_read_launch(int64_t n_entries, const int32_t* usid, const int32_t* emarket,
-                                  const int64_t* stamp_time_us, const int64_t* market_time_us, int64_t n_markets,
-                                  int32_t n_sources, const int64_t* poffsets, const int32_t* psid,
-                                  const double* prel, const double* pconf, const int64_t* pt_us, const uint8_t* phas,
-                                  int64_t n_rows, const int32_t* dentry, const int32_t* dqlast, const double* dtrace,
-                                  const double* drel, const double* dconf, const int64_t* dt_us,
-                                  const uint8_t* dhas, int64_t n_dentries, const int32_t* gqlast,
-                                  const double* gtrace, const double* grel, const double* gconf,
-                                  const int64_t* gt_us, const uint8_t* ghas, double half_life_days, double min_rel,
-                                  double default_rel, double default_conf, int mark_cold, int sid_clamped,
-                                  double* relconf, uint32_t* present_bits, uint8_t* scope, void* stream) {
+// bce_walk_scope_read_lag holds the launch; bce_walk_scope_read is the same with the two time arrays equal.
+extern "C" int bce_walk_scope_read_lag(int64_t n_entries, const int32_t* usid, const int32_t* emarket,
+                                       const int64_t* stamp_time_us, const int64_t* now_time_us, int64_t n_markets,
+                                       int32_t n_sources, const int64_t* poffsets, const int32_t* psid,
+                                       const double* prel, const double* pconf, const int64_t* pt_us,
+                                       const uint8_t* phas, int64_t n_rows, const int32_t* dentry,
+                                       const int32_t* dqlast, const double* dtrace, const double* drel,
+                                       const double* dconf, const int64_t* dt_us, const uint8_t* dhas,
+                                       int64_t n_dentries, const int32_t* gqlast, const double* gtrace,
+                                       const double* grel, const double* gconf, const int64_t* gt_us,
+                                       const uint8_t* ghas, double half_life_days, double min_rel, double default_rel,
+                                       double default_conf, int mark_cold, int sid_clamped, double* relconf,
+                                       uint32_t* present_bits, uint8_t* scope, void* stream) {
   BCE_REQUIRE(n_entries >= 0 && n_markets >= 0 && n_sources > 0 && n_rows >= 0 && n_dentries >= 0,
               "walk_scope_read: bad shape");
   BCE_REQUIRE(n_entries < (1ll << 31) && n_markets < (1ll << 31) && n_dentries < (1ll << 31),
               "walk_scope_read: n_entries, n_markets or n_dentries >= 2^31");
   BCE_REQUIRE(n_markets > 0 || n_entries == 0, "walk_scope_read: entries without markets");
   if (n_entries == 0 && !sid_clamped) return BCE_OK;
-  BCE_REQUIRE(n_entries == 0 || (usid && emarket && stamp_time_us && market_time_us),
+  BCE_REQUIRE(n_entries == 0 || (usid && emarket && stamp_time_us && now_time_us),
               "walk_scope_read: NULL argument");
   BCE_REQUIRE(n_entries == 0 || (relconf && present_bits && scope), "walk_scope_read: NULL output");
   BCE_REQUIRE(poffsets || n_rows == 0, "walk_scope_read: market rows without poffsets");
@@ -188,7 +189,7 @@ static int walk_scope_read_launch(int64_t n_entries, const int32_t* usid, const 
   a.usid = usid;
   a.emarket = emarket;
   a.stamp = stamp_time_us;
-  a.now = market_time_us;
+  a.now = now_time_us;
   a.M = n_markets;
   a.S = n_sources;
   a.poffsets = poffsets;
@@ -227,28 +228,9 @@ extern "C" int bce_walk_scope_read(int64_t n_entries, const int32_t* usid, const
                                    const int64_t* gt_us, const uint8_t* ghas, double half_life_days, double min_rel,
                                    double default_rel, double default_conf, int mark_cold, int sid_clamped,
                                    double* relconf, uint32_t* present_bits, uint8_t* scope, void* stream) {
-  return walk_scope_read_launch(n_entries, usid, emarket, market_time_us, market_time_us, n_markets, n_sources,
-                                poffsets, psid, prel, pconf, pt_us, phas, n_rows, dentry, dqlast, dtrace, drel, dconf,
-                                dt_us, dhas, n_dentries, gqlast, gtrace, grel, gconf, gt_us, ghas, half_life_days,
-                                min_rel, default_rel, default_conf, mark_cold, sid_clamped, relconf, present_bits,
-                                scope, stream);
-}
-
-extern "C" int bce_walk_scope_read_lag(int64_t n_entries, const int32_t* usid, const int32_t* emarket,
-                                       const int64_t* stamp_time_us, const int64_t* now_time_us, int64_t n_markets,
-                                       int32_t n_sources, const int64_t* poffsets, const int32_t* psid,
-                                       const double* prel, const double* pconf, const int64_t* pt_us,
-                                       const uint8_t* phas, int64_t n_rows, const int32_t* dentry,
-                                       const int32_t* dqlast, const double* dtrace, const double* drel,
-                                       const double* dconf, const int64_t* dt_us, const uint8_t* dhas,
-                                       int64_t n_dentries, const int32_t* gqlast, const double* gtrace,
-                                       const double* grel, const double* gconf, const int64_t* gt_us,
-                                       const uint8_t* ghas, double half_life_days, double min_rel, double default_rel,
-                                       double default_conf, int mark_cold, int sid_clamped, double* relconf,
-                                       uint32_t* present_bits, uint8_t* scope, void* stream) {
-  return walk_scope_read_launch(n_entries, usid, emarket, stamp_time_us, now_time_us, n_markets, n_sources, poffsets,
-                                psid, prel, pconf, pt_us, phas, n_rows, dentry, dqlast, dtrace, drel, dconf, dt_us,
-                                dhas, n_dentries, gqlast, gtrace, grel, gconf, gt_us, ghas, half_life_days, min_rel,
-                                default_rel, default_conf, mark_cold, sid_clamped, relconf, present_bits, scope,
-                                stream);
+  return bce_walk_scope_read_lag(n_entries, usid, emarket, market_time_us, market_time_us, n_markets, n_sources,
+                                 poffsets, psid, prel, pconf, pt_us, phas, n_rows, dentry, dqlast, dtrace, drel, dconf,
+                                 dt_us, dhas, n_dentries, gqlast, gtrace, grel, gconf, gt_us, ghas, half_life_days,
+                                 min_rel, default_rel, default_conf, mark_cold, sid_clamped, relconf, present_bits,
+                                 scope, stream);
 }

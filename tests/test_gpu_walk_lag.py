@@ -265,6 +265,43 @@ def test_without_lag_the_plan_and_the_walk_are_the_ordinary_ones(edge):
     N.check_faults(_dev(), "no lag")
 
 
+@pytest.mark.parametrize("all_present", [True, False])
+def test_both_read_entries_and_the_batch_read_write_the_same_bytes(edge, all_present):
+    """bce_walk_read(t), bce_walk_read_lag(t, t) and batch._walk_read with an ordinary plan, from one trace."""
+    e = edge
+    plan = batch.WalkPlan.build(*_args(e))
+    pp, E, M, S = plan.pairs, plan.pairs.n_entries, plan.pairs.n_markets, e["S"]
+    assert not plan.lagged and E % 32 and (plan.qlast == -1).any() and (plan.qlast >= 0).any()
+    for name, x in zip(("qstart", "qpos", "qentry", "qlast", "slast"), batch.WalkPlan.order(*_args(e))[1:6]):
+        assert torch.equal(getattr(plan, name), x) and getattr(plan.queries, name) is getattr(plan, name), name
+    table, mt = _table(e["state"]), _T(e["forecast"])
+    trace = torch.full((E, 2), -3.0, dtype=torch.float64, device=_dev())
+    batch._walk_settle_trace(plan, table, mt, trace, None, None)
+
+    def outputs():
+        return (torch.full((E, 2), -7.0, dtype=torch.float64, device=_dev()),
+                torch.full(((E + 31) // 32,), 0x5A5A5A5A, dtype=torch.int32, device=_dev()),
+                torch.full((E,), 77, dtype=torch.uint8, device=_dev()))
+
+    def args(times, out):
+        p = N.ptr
+        return [E, p(pp.usid), p(pp.emarket), p(plan.qlast), p(trace), *[p(t) for t in times], M, p(table.rel),
+                p(table.conf), p(table.t_us), p(table.present), S, batch.DECAY_HALF_LIFE_DAYS, batch.DECAY_MINIMUM,
+                batch.DEFAULT_RELIABILITY, batch.DEFAULT_CONFIDENCE, int(not all_present), 0, *[p(x) for x in out],
+                N.stream(_dev())]
+
+    old, new, glue = outputs(), outputs(), outputs()
+    L = N.lib()
+    N.check(L.bce_walk_read(*args((mt,), old)), "bce_walk_read")
+    N.check(L.bce_walk_read_lag(*args((mt, mt), new)), "bce_walk_read_lag")
+    batch._walk_read(plan, table, mt, trace, *glue, all_present, batch.DECAY_HALF_LIFE_DAYS, batch.DECAY_MINIMUM)
+    torch.cuda.synchronize()
+    N.check_faults(_dev(), "the three reads")
+    for name, x, y, z in zip(("relconf", "bits", "exists"), old, new, glue):
+        assert x.cpu().numpy().tobytes() == y.cpu().numpy().tobytes() == z.cpu().numpy().tobytes(), name
+    assert set(old[2].cpu().numpy().tolist()) == {0, 1} and not (old[0] == -7.0).any()  # written, cold sources seen
+
+
 def test_walk_sweep_on_a_lagged_plan_equals_every_point_run_alone(edge):
     e = edge
     plan = _lagged(e)

@@ -151,6 +151,39 @@ def test_small_batch_by_hand():
     _check(off, sid, [1, 1, 0, 1], md, 4, 2)
 
 
+def test_plans_hold_the_queries_order_returns():
+    """4 markets, 3 sources, 2 domains: market 0 sees source 0 twice, market 1 has no domain, market 2 is
+    unresolved.  A WalkPlan holds order()'s arrays as its ``q*`` fields and offers the very tensors as
+    ``queries``; a WalkScopePlan holds order()'s ``dq`` / ``gq``."""
+    off, sid = [0, 3, 5, 7, 10], [0, 2, 0, 1, 2, 0, 1, 0, 1, 2]
+    outcome, md = [1, 0, -1, 1], [0, -1, 1, 0]
+    fields = ("qstart", "qpos", "qentry", "qlast", "slast")
+    T = lambda a, dt: torch.tensor(np.asarray(a, dt))  # noqa: E731
+    args = (T(off, np.int64), T(sid, np.int32), T([0.5] * 10, np.float64), T(outcome, np.int8))
+    pairs, *q, nc = batch.WalkPlan.order(*args, 3)
+    # entries: (m0: 0, 2), (m1: 1, 2), (m2: 0, 1), (m3: 0, 1, 2); market 0 leaves two bits of source 0, market 2 none
+    assert [x.tolist() for x in q] == [[0, 3, 6, 9], [0, 2, 2, 0, 1, 1, 0, 1, 2], [0, 4, 6, 2, 5, 7, 1, 3, 8],
+                                       [-1, -1, -1, 0, 0, 1, 0, 1, 1], [3, 3, 3]]
+    plan = batch.WalkPlan(None, pairs, *q, nc, args[3])
+    assert not plan.lagged and plan.outcome is args[3] and isinstance(plan.queries, batch.WalkQueries)
+    for name, x in zip(fields, q):
+        assert getattr(plan.queries, name) is x and getattr(plan, name) is x, name
+    pairs, dplan, dentry, dq, gq, nc = batch.WalkScopePlan.order(*args, T(md, np.int32), 3, 2)
+    scoped = batch.WalkScopePlan(pairs, dplan, dentry, None, None, dq, gq, False, nc, args[3])
+    assert scoped.dq is dq and scoped.gq is gq and not scoped.lagged and scoped.outcome is args[3]
+    assert dentry.tolist() == [0, 2, -1, -1, 3, 4, 0, 1, 2]  # chains: (0, 0), (0, 1), (0, 2), (1, 0), (1, 1)
+    _, _, _, F, dfam, gfam = _restate(off, sid, outcome, md, 3, False)
+    assert F == dplan.n_entries == 5
+    for fam, got, exp in (("domain", scoped.dq, dfam), ("global", scoped.gq, gfam)):
+        for name, e in zip(fields, exp):
+            assert np.array_equal(getattr(got, name).numpy(), e), (fam, name)
+    assert scoped.gq.slast.tolist() == [-1, 1, 1] and scoped.dq.slast.tolist() == [3, 3, 3, -1, -1]
+    # with update_global every resolved market feeds the global family: the single-scope plan's queries
+    everything = batch.WalkScopePlan.order(*args, T(md, np.int32), 3, 2, True)[4]
+    for name, x in zip(fields, q):
+        assert torch.equal(getattr(everything, name), x) and getattr(everything, name).dtype == x.dtype, name
+
+
 @pytest.mark.parametrize("seed", range(6))
 def test_random_batches(seed):
     rng = np.random.default_rng(seed)
