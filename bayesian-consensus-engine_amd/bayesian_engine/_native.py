@@ -76,6 +76,8 @@ _SIGS = {
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "bce_consensus_history": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i32,
                                         _vp, _vp, _vp, _vp, _vp]),
+    "bce_consensus_leave_one_out": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i32,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bce_decay_view": (C.c_int, [_i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _vp, _vp]),
     "bce_decay_apply": (C.c_int, [_i64, _vp, _vp, _f64, _f64, _vp, _vp, _vp]),
     "bce_outcome_update": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _vp]),

@@ -12,7 +12,7 @@ Layout (include/bce.h):
 
 Every name lives in one submodule and is re-exported here; a submodule imports only from those
 listed before it: elementwise, tables, consensus, tiebreak, stats, reestimate_csr, settle, pairs,
-walk, glob, score, history, bootstrap (which imports from score only).
+walk, glob, score, history, leave_one_out, bootstrap (which imports from score only).
 """
 from .elementwise import (DECAY_HALF_LIFE_DAYS, DECAY_MINIMUM, DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY, decay_apply,
                           decay_view, outcome_update, pack_flags2, replay_step)
@@ -40,5 +40,6 @@ from .score import (SCORE_COUNTS, SCORE_LANES, SCORE_MAX_BINS, SCORE_SEG, SCORE_
                     walk_sweep_scoped)
 from .history import (HISTORY_MAX_LEN, HistoryResult, _history_items, _market_of_point, consensus_history, history_at,
                       score_history, walk_history)
+from .leave_one_out import (LeaveOneOutResult, _loo_items, leave_one_out, score_leave_one_out, walk_leave_one_out)
 from .bootstrap import (BOOT_COUNTS, BOOT_MAX_SETS, BOOT_METRICS, BOOT_TILE, BootstrapResult, boot_units, boot_weights,
                         score_bootstrap)

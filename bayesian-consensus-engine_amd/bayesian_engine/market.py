@@ -140,6 +140,32 @@ class Market:
         return _history_rows(self.signals, *(x.cpu().numpy() for x in (h.consensus, h.confidence, h.total_weight,
                                                                        h.n_unique)))
 
+    def leave_one_out(self, source_reliability: Optional[Dict[str, Dict[str, float]]] = None
+                      ) -> List[Dict[str, Any]]:
+        """What the consensus would be without each source, in one launch
+        (``batch.leave_one_out``): one entry per sourceId in sorted() order, ``{"sourceId",
+        "consensus": a float or None, "confidence", "totalWeight", "sourceCount", "influence"}``.
+        The first four equal the corresponding fields of ``compute_consensus([s for s in
+        self.signals if s["sourceId"] != sourceId], source_reliability)`` -- dropping the only source
+        gives the values of a market without signals (core.py:88-96).  ``influence`` is the market's
+        consensus minus that consensus, None where either is None.  An empty market gives ``[]``;
+        ``consensus_result`` is not touched."""
+        if not self.signals:
+            return []
+        rel = source_reliability or {}
+        ids = sorted({s["sourceId"] for s in self.signals})  # core.py:103
+        rank = {sid: i for i, sid in enumerate(ids)}
+        off, sid, prob = signals_csr([self.signals], rank)
+        rows = [rel.get(i, {}) for i in ids]  # core.py:110-112
+        N.require_gpu()
+        T = batch.to_device(N.device())
+        table = batch.SourceTable.from_arrays(
+            T(np.array([float(r.get("reliability", DEFAULT_RELIABILITY)) for r in rows], np.float64)),
+            T(np.array([float(r.get("confidence", DEFAULT_CONFIDENCE)) for r in rows], np.float64)),
+            T(np.array([i in rel for i in ids], np.uint8)), ids)
+        loo = batch.leave_one_out(T(off), T(sid), T(prob), table, offsets_host=off, check=True)
+        return _leave_one_out_rows(ids, sid, *_loo_host(loo), 0, 0, len(sid))
+
     def resolve(self, outcome: bool) -> None:
         self.outcome = outcome
         self.status = MarketStatus.RESOLVED
@@ -258,6 +284,17 @@ class MarketStore:
         computed = _batched_history(busy, reliability_store) if busy else {}
         return {str(m.id): computed.get(str(m.id), []) for m in markets}
 
+    def compute_all_leave_one_out(self, reliability_store: Optional[SQLiteReliabilityStore] = None
+                                  ) -> Dict[str, List[Dict[str, Any]]]:
+        """``Market.leave_one_out`` for all open markets in ONE batched launch: market id -> the
+        list of its entries (``[]`` for a market without signals), over the table
+        ``compute_all_consensus`` reads (:meth:`compute_all_history`).  No market's
+        ``consensus_result`` is touched."""
+        markets = self.list_markets(status=MarketStatus.OPEN)
+        busy = [m for m in markets if m.signals]
+        computed = _batched_leave_one_out(busy, reliability_store) if busy else {}
+        return {str(m.id): computed.get(str(m.id), []) for m in markets}
+
 
 def _domain_fn(domain_of):
     """``domain_of=``: a callable ``Market -> Optional[str]``, or "category" (MarketId.category)."""
@@ -277,7 +314,8 @@ class _FirstSeen(dict):
 
 
 def _batched_table(markets: List[Market], store: Optional[SQLiteReliabilityStore]):
-    """The batch ``_batched_consensus`` and ``_batched_history`` run on: CSR over the markets, ranks
+    """The batch ``_batched_consensus``, ``_batched_history`` and ``_batched_leave_one_out`` run on:
+    CSR over the markets, ranks
     over (market position, sorted sourceId), and the consensus table over those ranks -- with a
     store, every (source, market) pair fetched and decayed at "now".  Returns ``(per_market_ids,
     off, (offsets, sid, prob) on the device, table)``."""
@@ -342,6 +380,43 @@ def _batched_history(markets: List[Market], store: Optional[SQLiteReliabilitySto
     cons, confd, tot, nu = (x.cpu().numpy() for x in (h.consensus, h.confidence, h.total_weight, h.n_unique))
     return {str(m.id): _history_rows(m.signals, cons[a:b], confd[a:b], tot[a:b], nu[a:b])
             for m, a, b in zip(markets, off[:-1], off[1:])}
+
+
+def _loo_host(loo):
+    """A :class:`batch.LeaveOneOutResult` as host arrays: the four per-signal ones, then the full
+    consensus and total weight per market."""
+    return tuple(x.cpu().numpy() for x in (loo.consensus, loo.confidence, loo.total_weight, loo.n_unique,
+                                           loo.full.consensus, loo.full.total_weight))
+
+
+def _leave_one_out_rows(ids, sid, cons, confd, tot, nu, full_cons, full_tot, mpos, a, b) -> List[Dict[str, Any]]:
+    """``Market.leave_one_out``'s entries for the market at batch position ``mpos`` with signals
+    ``[a, b)``: ``ids`` its sourceIds in sorted() order, ``sid`` the batch's ranks (ascending with
+    ``ids`` inside the market); a source's values are read at its first signal."""
+    first: Dict[int, int] = {}
+    for p in range(a, b):
+        first.setdefault(int(sid[p]), p)
+    full_null = full_tot[mpos] == 0  # core.py:131
+    rows = []
+    for name, s in zip(ids, sorted(first)):
+        p = first[s]
+        null = tot[p] == 0  # nothing left, or no weight left
+        rows.append({"sourceId": name, "consensus": None if null else float(cons[p]),
+                     "confidence": 0.0 if null else float(confd[p]), "totalWeight": float(tot[p]),
+                     "sourceCount": int(nu[p]),
+                     "influence": None if null or full_null else float(full_cons[mpos] - cons[p])})
+    return rows
+
+
+def _batched_leave_one_out(markets: List[Market], store: Optional[SQLiteReliabilityStore]
+                           ) -> Dict[str, List[Dict[str, Any]]]:
+    """One launch (``batch.leave_one_out``) over the batch of :func:`_batched_table`."""
+    per_market_ids, off, csr, table = _batched_table(markets, store)
+    loo = batch.leave_one_out(*csr, table, offsets_host=off, check=True)
+    host = _loo_host(loo)
+    sid = csr[1].cpu().numpy()
+    return {str(m.id): _leave_one_out_rows(ids, sid, *host, mpos, int(off[mpos]), int(off[mpos + 1]))
+            for mpos, (m, ids) in enumerate(zip(markets, per_market_ids))}
 
 
 def _render_markets(markets: List[Market], per_market_ids, offsets, res) -> Dict[str, Dict[str, Any]]:
@@ -944,6 +1019,41 @@ class CrossMarketAggregator:
                                              float(skill[i])) for i, name in enumerate(names)}
         N.check_faults(dev, "score_walk")
         return out
+
+    def source_influence(self, patterns: Optional[List[str]] = None,
+                         reliability_store: Optional[SQLiteReliabilityStore] = None,
+                         n_bins: int = 10) -> Dict[str, SourceScore]:
+        """Was the consensus better or worse for having each source?  Over the selected markets
+        that have signals (as ``reestimate_sources`` selects them), every market's consensus is
+        computed with and without each of its sources in one launch (``batch.leave_one_out``, over
+        the table ``compute_all_consensus`` reads) and scored against the store's own outcome, read
+        as ``score_walk`` reads it.  Returns a :class:`SourceScore` per sourceId, interned in
+        first-seen order as ``summarize_sources`` does, one item per (market, source)
+        (``batch.score_leave_one_out(per="pair")``): ``n`` the scored markets of the source,
+        ``brier`` / ``log_loss`` / ``accuracy`` those of the consensus WITHOUT the source, and
+        ``skill`` that Brier score minus the full consensus's over the same markets -- positive:
+        the consensus is worse without the source."""
+        B = int(n_bins)
+        if not 1 <= B <= batch.SCORE_MAX_BINS:
+            raise ValueError(f"n_bins must be in [1, {batch.SCORE_MAX_BINS}] (got {n_bins})")
+        markets = self._select(None, patterns, None, with_signals=True)
+        if not markets:
+            return {}
+        code = np.array([(1 if m.outcome else 0) if m.status == MarketStatus.RESOLVED and m.outcome is not None
+                         else -1 for m in markets], np.int8)
+        order = _FirstSeen()
+        gsid = np.array([order[s["sourceId"]] for m in markets for s in m.signals], np.int32)
+        names = list(order)
+        _, off, csr, table = _batched_table(markets, reliability_store)
+        dev = N.device()
+        T = batch.to_device(dev)
+        loo = batch.leave_one_out(*csr, table, offsets_host=off, check=True)
+        ss = batch.score_leave_one_out(loo, csr[0], T(gsid), T(code), len(names), per="pair", n_bins=B)
+        n, brier, ll, acc, skill = (x.cpu().numpy() for x in (ss.n_scored, ss.brier, ss.log_loss, ss.accuracy,
+                                                               ss.skill))
+        N.check_faults(dev, "source_influence")
+        return {name: SourceScore(name, int(n[i]), float(brier[i]), float(ll[i]), float(acc[i]), float(skill[i]))
+                for i, name in enumerate(names)}
 
     def sweep_decay(self, store, half_life_days, min_rel, patterns: Optional[List[str]] = None,
                     domain: Optional[str] = None, n_bins: int = 10,

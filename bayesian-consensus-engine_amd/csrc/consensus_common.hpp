@@ -4,6 +4,7 @@
 // consensus_lane.hpp; consensus_tab.hip: the LDS-table kernel for contiguous short markets;
 // consensus_wide.hip: 64 < n <= 4096, its sort network in wide_sort.hpp and its chain loops in
 // ordered_chain.hpp; consensus_history.hip: every market's consensus after each signal;
+// consensus_leave_one_out.hip: every market's consensus without each of its sources;
 // consensus_api.hip: the C entries that pick among them; plan.hip: the planners), and the few
 // device pieces every one of them writes the same way.
 #pragma once

@@ -24,6 +24,7 @@
 // clamped and raises kFaultSid.  Keys are 64 bits wide ((sid << 32) | position): any table size.
 // No floating-point atomics; every output element has exactly one writer.
 #include "consensus_common.hpp"
+#include "consensus_history.hpp"
 #include "plan_host.hpp"
 
 #pragma clang fp contract(off)
@@ -31,20 +32,7 @@
 namespace bce {
 namespace {
 
-constexpr int kHistMaxThreads = 1024;
 constexpr int kHistElemBytes = 32;  // LDS per signal of the long kernel: key, probability, row
-
-// A signal's sid as its table row: clamped into [0, n_sources) (unsigned compare, so a negative
-// sid clamps to the last row); `bad` is set when it was outside.
-__device__ __forceinline__ unsigned hist_row(int32_t sid, int32_t n_sources, bool& bad) {
-  const unsigned smax = n_sources > 0 ? (unsigned)(n_sources - 1) : 0u;
-  const unsigned s = (unsigned)sid;
-  bad = bad || s > smax || n_sources <= 0;
-  return s < smax ? s : smax;
-}
-__device__ __forceinline__ double2 hist_gather(const ConsArgs& a, unsigned row) {
-  return a.n_sources > 0 ? a.relconf[row] : make_double2(0.0, 0.0);
-}
 
 // Point k of a market of n signals sorted by (sid, position): key[e] = (sid << 32) | position,
 // prob[e] and row[e] the probability and the table row of sorted element e.  The elements with

@@ -234,6 +234,36 @@ int bce_consensus_history(const int64_t* offsets, int64_t n_markets, const int32
                           double* consensus, double* confidence, double* total_weight, int32_t* n_unique,
                           void* stream);
 
+/* ---- leave-one-source-out consensus: every source's marginal effect on its market ----
+ *
+ * Replaces: compute_consensus([s for s in signals if s["sourceId"] != x], table) for every
+ * source x of every market (core.py:63-180).  The signal at CSR position p, of source x in
+ * market m, gets the consensus of m's signals whose source is not x: consensus (0.0 where the
+ * reference returns None, core.py:131-133), confidence (0.0 there too), total_weight, n_unique
+ * (the market's unique sources less one); null <=> total_weight == 0, which includes "nothing is
+ * left".  All four outputs have n_signals elements; all signals of one source in one market hold
+ * the same values.  full_* (each [n_markets]; all four NULL or all four non-NULL) receive the
+ * market's own consensus, bit-identical to bce_consensus_csr in exact mode; the row of an empty
+ * market is zeros.  Exact order only; no per-unique outputs.
+ *
+ * Every signal is read once (the expansion into one reduced market per signal reads about U - 1
+ * times as many, U the market's unique sources).  A market is sorted once, every source's
+ * average and products are formed once, and leave-out j is the ordered sum of the three columns
+ * over the other sources: O(n + U^2) per market.
+ *
+ * The arguments before the outputs, the three launch routes, the fault word (a market over 4096
+ * signals or over the bound of a max_len <= 64 launch is left untouched; a sid outside
+ * [0, n_sources) has its row read clamped) and the BCE_EINVAL checks are those of
+ * bce_consensus_history.  Positions and full_* rows of markets outside the list or the plan are
+ * left untouched. */
+int bce_consensus_leave_one_out(const int64_t* offsets, int64_t n_markets, const int32_t* sid, const double* prob,
+                                int64_t n_signals, const double* relconf, const uint32_t* present_bits,
+                                int32_t n_sources, const int32_t* market_list, int64_t n_list,
+                                const int64_t* bin_start_host, const int64_t* bin_start_dev, int32_t max_len,
+                                double* consensus, double* confidence, double* total_weight, int32_t* n_unique,
+                                double* full_consensus, double* full_confidence, double* full_total_weight,
+                                int32_t* full_n_unique, void* stream);
+
 /* ---- decay: get_reliability(apply_decay=True) over a table ----------------------
  * Replaces: decay.apply_reliability_decay (decay.py:61-100) composed with
  * decay.days_since_update (decay.py:103-145) as used by
