@@ -25,6 +25,7 @@ NBINS = 13  # include/bce.h BCE_NBINS
 PAIR_STORE, PAIR_NAMESPACED, PAIR_RAW = 0, 1, 2  # include/bce.h bce_pair_mode
 SCORE_MAX_BINS, SCORE_SEG, SCORE_LANES = 32, 2048, 256  # include/bce.h BCE_SCORE_*
 BOOT_MAX_SETS, BOOT_TILE = 8, 256  # include/bce.h BCE_BOOT_*
+UPDATE_MAX_POINTS = 64  # include/bce.h BCE_UPDATE_MAX_POINTS
 NO_TIMESTAMP = -(2**63)
 TB_LABELS = {0: "unanimous", 1: "weight_density", 2: "prediction_value_smallest", 3: "unanimous"}
 
@@ -105,6 +106,8 @@ _SIGS = {
                                    _i64, _f64, _f64, _vp, _vp]),
     "bce_settle_trace": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _f64,
                                    _f64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "bce_settle_trace_grid": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _f64,
+                                        _f64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
     "bce_walk_read": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _f64, _f64, _f64,
                                 _f64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "bce_walk_lag_queries": (C.c_int, [_i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp,

@@ -12,7 +12,8 @@ Layout (include/bce.h):
 
 Every name lives in one submodule and is re-exported here; a submodule imports only from those
 listed before it: elementwise, tables, consensus, tiebreak, stats, reestimate_csr, settle, pairs,
-walk, glob, score, history, leave_one_out, bootstrap (which imports from score only).
+walk, glob, score, history, leave_one_out, bootstrap (which imports from score only), update_sweep
+(which imports from walk and score).
 """
 from .elementwise import (DECAY_HALF_LIFE_DAYS, DECAY_MINIMUM, DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY, decay_apply,
                           decay_view, outcome_update, pack_flags2, replay_step)
@@ -43,3 +44,4 @@ from .history import (HISTORY_MAX_LEN, HistoryResult, _history_items, _market_of
 from .leave_one_out import (LeaveOneOutResult, _loo_items, leave_one_out, score_leave_one_out, walk_leave_one_out)
 from .bootstrap import (BOOT_COUNTS, BOOT_MAX_SETS, BOOT_METRICS, BOOT_TILE, BootstrapResult, boot_units, boot_weights,
                         score_bootstrap)
+from .update_sweep import (UPDATE_MAX_POINTS, commit_update_point, update_steps, walk_sweep_update, walk_trace_grid)

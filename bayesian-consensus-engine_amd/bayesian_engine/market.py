@@ -34,7 +34,7 @@ import torch
 
 from . import _native as N
 from . import batch
-from .config import DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY
+from .config import DECAY_HALF_LIFE_DAYS, DECAY_MINIMUM, DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY, MAX_UPDATE_STEP
 from .core import compute_consensus, consensus_dict, signals_csr
 from .reliability import SQLiteReliabilityStore
 from .reliability_abstraction import NamespacedReliabilityStore, _check_boot
@@ -614,9 +614,11 @@ def _compare_arguments(what, store, half_life_days, min_rel, n_boot, block, metr
     return hl, mr
 
 
-def _comparison(run, hl, mr, metric, level, reference, n_boot, seed, block) -> "DecayComparison":
-    """The :class:`DecayComparison` of a store's ``(scores, boot)`` (None: no signals)."""
-    params = [{"half_life_days": h, "min_rel": m} for h in hl for m in mr]
+def _comparison(run, hl, mr, metric, level, reference, n_boot, seed, block, params=None) -> "DecayComparison":
+    """The :class:`DecayComparison` of a store's ``(scores, boot)`` (None: no signals); ``params``:
+    the grid points where they are not the decay grid alone."""
+    if params is None:
+        params = [{"half_life_days": h, "min_rel": m} for h in hl for m in mr]
     level = float(level)
     if run is None:
         rows = [DecayRow(p, 0, None, None, None, None, None, None, None, None) for p in params]
@@ -673,9 +675,25 @@ def _sweep_arguments(what: str, store, half_life_days, min_rel, n_bins):
     return hl, mr, B
 
 
-def _sweep_rows(scores, hl, mr, B) -> List["BacktestScore"]:
-    """One :class:`BacktestScore` per grid point of a store sweep (None: a history without signals)."""
-    params = [{"half_life_days": h, "min_rel": m} for h in hl for m in mr]
+def _update_arguments(what: str, store, learning_rate, max_step, half_life_days, min_rel, n_bins):
+    """The checked arguments of an update-rule sweep: ``(params, half_life_days, min_rel,
+    n_bins)``, ``params`` one dict per grid point, the update point slowest."""
+    hl, mr, B = _sweep_arguments(what, store, half_life_days, min_rel, n_bins)
+    batch.update_steps(learning_rate, max_step)  # TypeError / ValueError
+    lr = [float(x) for x in np.atleast_1d(np.asarray(learning_rate, np.float64))]
+    ms = [float(x) for x in np.atleast_1d(np.asarray(max_step, np.float64))]
+    if len(ms) == 1:
+        ms = ms * len(lr)
+    params = [{"learning_rate": r, "max_step": c, "half_life_days": h, "min_rel": m}
+              for r, c in zip(lr, ms) for h in hl for m in mr]
+    return params, hl, mr, B
+
+
+def _sweep_rows(scores, hl, mr, B, params=None) -> List["BacktestScore"]:
+    """One :class:`BacktestScore` per grid point of a store sweep (None: a history without
+    signals); ``params``: the grid points where they are not the decay grid alone."""
+    if params is None:
+        params = [{"half_life_days": h, "min_rel": m} for h in hl for m in mr]
     if scores is None:
         return [BacktestScore.empty(B, p) for p in params]
     flat = batch.ScoreResult(*(getattr(scores, k)[:, 0] for k in ("counts", "sums", "bin_n", "bin_pos", "bin_psum")))
@@ -1122,6 +1140,50 @@ class CrossMarketAggregator:
         run = store.compare_decay_namespaced(batch_markets, stamps, hl, mr, resolve_times=resolve_stamps,
                                              n_boot=n_boot, seed=seed, block=block, **kw)
         return _comparison(run, hl, mr, metric, level, reference, n_boot, seed, block)
+
+    def sweep_update(self, store, learning_rate, max_step=MAX_UPDATE_STEP, half_life_days=(DECAY_HALF_LIFE_DAYS,),
+                     min_rel=(DECAY_MINIMUM,), patterns: Optional[List[str]] = None, domain: Optional[str] = None,
+                     n_bins: int = 10, device_match: Optional[bool] = None,
+                     lagged: bool = False) -> List["BacktestScore"]:
+        """:meth:`sweep_decay` over the update rule: you edited ``_BASE_LEARNING_RATE`` /
+        ``MAX_UPDATE_STEP`` to tune the engine -- this is the back-test of ``walk_forward(store,
+        patterns, domain, dry_run=True)`` as if they were ``(learning_rate[i], max_step[i])``
+        (pairs; ``max_step`` one number for all or one per point), for every update point and
+        every point of the decay grid: one whole-history :class:`BacktestScore` per point,
+        update point slowest, ``min_rel`` fastest (``params`` names it: ``learning_rate``,
+        ``max_step``, ``half_life_days``, ``min_rel``).  All update points are traced in one
+        launch (``store.sweep_update``, ``batch.walk_sweep_update``); nothing is written to the
+        store.  The single-scope walk only."""
+        params, hl, mr, B = _update_arguments("sweep_update", store, learning_rate, max_step, half_life_days,
+                                              min_rel, n_bins)
+        _, batch_markets, stamps, resolve_stamps = self._walk_history(patterns, device_match, lagged)
+        scores = store.sweep_update(batch_markets, stamps, learning_rate, max_step, hl, mr, domain=domain, n_bins=B,
+                                    resolve_times=resolve_stamps)
+        return _sweep_rows(scores, hl, mr, B, params)
+
+    def compare_update(self, store, learning_rate, max_step=MAX_UPDATE_STEP, half_life_days=(DECAY_HALF_LIFE_DAYS,),
+                       min_rel=(DECAY_MINIMUM,), patterns: Optional[List[str]] = None, domain: Optional[str] = None,
+                       lagged: bool = False, device_match: Optional[bool] = None, n_boot: int = 1000, seed: int = 0,
+                       block: int = 1, metric: str = "brier", level: float = 0.95,
+                       reference: Optional[int] = None) -> "DecayComparison":
+        """:meth:`compare_decay` over the grid of :meth:`sweep_update`: the same walk and sweep,
+        then the paired bootstrap over the markets (``store.compare_update``).  Returns a
+        :class:`DecayComparison` whose rows carry the four ``params`` of :meth:`sweep_update`."""
+        params, hl, mr, _ = _update_arguments("compare_update", store, learning_rate, max_step, half_life_days,
+                                              min_rel, 10)
+        _check_boot(n_boot, block)
+        if isinstance(reference, bool) or not (reference is None or isinstance(reference, (int, np.integer))):
+            raise TypeError(f"reference must be a grid index or None (got {type(reference).__name__})")
+        if reference is not None and not 0 <= reference < len(params):
+            raise ValueError(f"reference must be a grid index in [0, {len(params)}) (got {reference})")
+        if metric not in COMPARE_METRICS or metric == "skill":
+            raise ValueError(f"metric must be one of {COMPARE_METRICS[:3]} (got {metric!r})")
+        if not 0.0 < float(level) < 1.0:
+            raise ValueError(f"level must be in (0, 1) (got {level})")
+        _, batch_markets, stamps, resolve_stamps = self._walk_history(patterns, device_match, lagged)
+        run = store.compare_update(batch_markets, stamps, learning_rate, max_step, hl, mr, domain=domain,
+                                   resolve_times=resolve_stamps, n_boot=n_boot, seed=seed, block=block)
+        return _comparison(run, hl, mr, metric, level, reference, n_boot, seed, block, params)
 
     def summarize_category(self, category: str) -> Dict[str, Any]:
         markets = self._store.list_markets(pattern=f"{category}:*")

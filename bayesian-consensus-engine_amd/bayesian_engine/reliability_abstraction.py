@@ -23,7 +23,7 @@ import torch
 
 from . import _native as N
 from . import batch
-from .config import DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY
+from .config import DECAY_HALF_LIFE_DAYS, DECAY_MINIMUM, DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY, MAX_UPDATE_STEP
 from .core import _no_signals as core_no_signals, consensus_dict, signals_csr
 from .reliability import SQLiteReliabilityStore
 from .timeutil import NO_TIMESTAMP, dt_to_us, iso_to_us, us_to_iso
@@ -563,6 +563,50 @@ class NamespacedReliabilityStore:
         b = self._scope_walk(markets, times, self._update_scope(domain)[2], resolve_times)[-1]
         run = self._sweep_run(b, half_life_days, min_rel, 10, True, "compare_decay")
         return None if run is None else self._compare(*run, n_boot, seed, block, "compare_decay")
+
+    @staticmethod
+    def _update_run(b, learning_rate, max_step, half_life_days, min_rel, n_bins, keep_consensus, what):
+        """:meth:`_sweep_run` with the update rule as the slowest axis (:func:`batch.walk_sweep_update`)."""
+        if b is None:
+            return None
+        scores, kept = batch.walk_sweep_update(b.plan, b.table, b.mtime, offsets=b.off, prob=b.prob,
+                                               learning_rate=learning_rate, max_step=max_step,
+                                               half_life_days=half_life_days, min_rel=min_rel, n_bins=n_bins,
+                                               keep_consensus=keep_consensus)
+        N.check_faults(b.off.device, what)
+        return scores, kept, b.plan.outcome
+
+    def sweep_update(self, markets: Sequence[tuple], stamps: Sequence, learning_rate, max_step=MAX_UPDATE_STEP,
+                     half_life_days: Sequence[float] = (DECAY_HALF_LIFE_DAYS,),
+                     min_rel: Sequence[float] = (DECAY_MINIMUM,), domain: Optional[str] = None, n_bins: int = 10,
+                     resolve_times: Optional[Sequence] = None):
+        """:meth:`sweep_decay` over the update rule itself: :meth:`walk_forward` as a dry run as if
+        ``_BASE_LEARNING_RATE`` / ``MAX_UPDATE_STEP`` were ``(learning_rate[i], max_step[i])`` --
+        pairs, ``max_step`` one number for all or one per point (:func:`batch.update_steps`) --
+        for every update point and every point of the decay grid, each scored against the
+        batch's outcomes (:func:`batch.walk_sweep_update`: all update points are traced in one
+        launch).  Nothing is written.  Returns the :class:`batch.ScoreResult` of the whole history
+        with a leading grid dimension ``[K * len(half_life_days) * len(min_rel), 1, ...]`` (update
+        point slowest, ``min_rel`` fastest), or None for a history without signals.  ``stamps`` /
+        ``resolve_times`` are :meth:`walk_forward`'s ``times`` / ``resolve_times``."""
+        batch.update_steps(learning_rate, max_step)  # the argument errors, before anything is loaded
+        b = self._scope_walk(markets, stamps, self._update_scope(domain)[2], resolve_times)[-1]
+        run = self._update_run(b, learning_rate, max_step, half_life_days, min_rel, n_bins, False, "sweep_update")
+        return None if run is None else run[0]
+
+    def compare_update(self, markets: Sequence[tuple], stamps: Sequence, learning_rate, max_step=MAX_UPDATE_STEP,
+                       half_life_days: Sequence[float] = (DECAY_HALF_LIFE_DAYS,),
+                       min_rel: Sequence[float] = (DECAY_MINIMUM,), domain: Optional[str] = None,
+                       resolve_times: Optional[Sequence] = None, n_boot: int = 1000, seed: int = 0, block: int = 1):
+        """:meth:`sweep_update` with the paired bootstrap of :meth:`compare_decay`: the same sweep
+        (``keep_consensus=True``) into :func:`batch.score_bootstrap`, one forecast set per grid
+        point.  Nothing is written.  Returns ``(scores, boot)`` or None for a history without
+        signals."""
+        _check_boot(n_boot, block)
+        batch.update_steps(learning_rate, max_step)
+        b = self._scope_walk(markets, stamps, self._update_scope(domain)[2], resolve_times)[-1]
+        run = self._update_run(b, learning_rate, max_step, half_life_days, min_rel, 10, True, "compare_update")
+        return None if run is None else self._compare(*run, n_boot, seed, block, "compare_update")
 
     def _namespaced_walk(self, markets, times, domains, market_ids, update_global, resolve_times):
         """What :meth:`walk_forward_namespaced` and :meth:`sweep_decay_namespaced` share: the

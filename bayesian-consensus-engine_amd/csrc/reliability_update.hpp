@@ -16,6 +16,13 @@ __device__ __forceinline__ void update_rel(double& r, bool correct) {
   r = py_max(0.0, py_min(1.0, r + capped));
 }
 
+// update_rel under another rule.  With direction = +-1.0, learning rate >= 0 and cap >= 0 the
+// reference's capped step max(-cap, min(cap, rate * direction)) is exactly +-delta with delta =
+// min(cap, rate): selection and negation, no arithmetic, so one double per rule is bit-exact.
+__device__ __forceinline__ void update_rel_step(double& r, bool correct, double delta) {
+  r = py_max(0.0, py_min(1.0, r + (correct ? delta : -delta)));
+}
+
 // reliability.py:172-173: each update closes 10% of the gap to 1.0.
 __device__ __forceinline__ void update_conf(double& c) { c = py_min(1.0, c + (1.0 - c) * 0.10); }
 

@@ -61,13 +61,30 @@ __device__ __forceinline__ double settle_conf(double c, int64_t n) {
   return c;
 }
 
+// The update rule a chain is walked under: the step of one bit, and whether a run of equal bits
+// has pinned the reliability.  FixedRule is the reference's constants, compiled in.
+struct FixedRule {
+  __device__ __forceinline__ void step(double& r, bool correct) const { update_rel(r, correct); }
+  __device__ __forceinline__ bool pinned(int run) const { return run >= kSyncRun; }
+};
+
+// One point of an update-rule grid: the step delta = min(cap, rate) and the run of equal bits
+// that pins r to exactly 1.0 / 0.0 under it (the caller's bound; kNeverSync: no run does).
+constexpr int kNeverSync = 0x7fffffff;
+struct StepRule {
+  double delta;
+  int sync;
+  __device__ __forceinline__ void step(double& r, bool correct) const { update_rel_step(r, correct, delta); }
+  __device__ __forceinline__ bool pinned(int run) const { return run >= sync; }
+};
+
 // Chain positions [p0, p1) of the chain that starts at bit b0, word by word (the lane streams its
-// own words).  WALK: every bit is one update_rel on r.  TRACK: run / prev follow the length of the
-// current run of equal bits; the first position that completes kSyncRun equal bits ends the span
+// own words).  WALK: every bit is one step of `rule` on r.  TRACK: run / prev follow the length of
+// the current run of equal bits; the first position that completes a pinning run ends the span
 // (its bit already applied) and is returned, else -1.
-template <bool WALK, bool TRACK>
+template <bool WALK, bool TRACK, class Rule>
 __device__ __forceinline__ int64_t settle_span(const unsigned long long* __restrict__ bits, int64_t b0, int64_t p0,
-                                               int64_t p1, double& r, int& run, bool& prev) {
+                                               int64_t p1, double& r, int& run, bool& prev, const Rule& rule) {
   int64_t g = b0 + p0;
   const int64_t gend = b0 + p1;
   while (g < gend) {
@@ -78,16 +95,23 @@ __device__ __forceinline__ int64_t settle_span(const unsigned long long* __restr
     for (int k = 0; k < n; ++k) {
       const bool bit = (w & 1ull) != 0;
       w >>= 1;
-      if (WALK) update_rel(r, bit);
+      if (WALK) rule.step(r, bit);
       if (TRACK) {
         run = (run > 0 && bit == prev) ? run + 1 : 1;
         prev = bit;
-        if (run >= kSyncRun) return g + k - b0;
+        if (rule.pinned(run)) return g + k - b0;
       }
     }
     g += n;
   }
   return -1;
+}
+
+// Under the reference's constants: a run of kSyncRun equal bits pins.
+template <bool WALK, bool TRACK>
+__device__ __forceinline__ int64_t settle_span(const unsigned long long* __restrict__ bits, int64_t b0, int64_t p0,
+                                               int64_t p1, double& r, int& run, bool& prev) {
+  return settle_span<WALK, TRACK>(bits, b0, p0, p1, r, run, prev, FixedRule{});
 }
 
 }  // namespace bce

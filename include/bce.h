@@ -539,6 +539,35 @@ int bce_walk_read(int64_t n_entries, const int32_t* usid, const int32_t* emarket
                   int mark_cold, int sid_clamped, double* relconf, uint32_t* present_bits, uint8_t* exists,
                   void* stream);
 
+/* ---- the settlement trace under a grid of update rules ----------------------------------------
+ * update_reliability's step is max(-MAX_UPDATE_STEP, min(MAX_UPDATE_STEP, _BASE_LEARNING_RATE *
+ * direction)) with direction = +-1.0 (reliability.py:163-169): for a rate >= 0 and a cap >= 0
+ * exactly +-delta with delta = min(cap, rate).  bce_settle_trace_grid is bce_settle_trace (the
+ * same arguments up to n_entries, the same workers and faults) for n_points rules at once, over
+ * one read of the bits and the queries: rule k walks every chain with step[k] = delta_k and
+ * stores its states into trace[2 * (k * n_entries + qentry)] -- n_points traces back to back,
+ * each as bce_settle_trace writes it, so bce_walk_read / bce_walk_read_lag take slice k
+ * unchanged.  The confidence chain does not depend on the rule.
+ *
+ * sync_run[k]: the number of equal bits in a row that pin the reliability to exactly 1.0 / 0.0
+ * under delta_k, whatever it was before -- the caller's bound, ceil(1 / delta) + 1 for delta >=
+ * 2^-20 (11 for 0.1) -- or <= 0: no run does (delta == 0, or a delta too small to bound: the
+ * chain's first worker then walks all of it).  It matters on the long path only, and a value that
+ * is no bound gives wrong states there, not a fault.
+ *
+ * final (nullable, 16-byte aligned, [n_points * n_sources * 2]): {rel, conf} after the whole
+ * chain of every touched source under rule k at final[2 * (k * n_sources + s)]; the other
+ * sources are not written.  A step that is negative or NaN raises the fault word and its rule is
+ * not traced.  n_points outside [1, BCE_UPDATE_MAX_POINTS], a NULL step or sync_run, a trace or
+ * final that is not 16-byte aligned, chunk_bits >= 2^31: BCE_EINVAL. */
+#define BCE_UPDATE_MAX_POINTS 64
+int bce_settle_trace_grid(const uint64_t* bits, int64_t n_bits, const int64_t* start, const int32_t* order,
+                          int64_t n_touched, int64_t n_long, const int64_t* chunk_start, int64_t n_chunks,
+                          int64_t chunk_bits, int32_t n_sources, const double* rel, const double* conf,
+                          const uint8_t* present, double default_rel, double default_conf, const int64_t* qstart,
+                          const int64_t* qpos, const int32_t* qentry, int64_t n_entries, const double* step,
+                          const int64_t* sync_run, int32_t n_points, double* trace, double* final, void* stream);
+
 /* ---- walk-forward with resolution lag: a forecast time and a resolve time per market ----------
  * The reference as an event loop, the events sorted by (time, market, kind): F_m = (forecast_time_us
  * [m], m, 0) scores market m with every source read at that time, R_m = (resolve_time_us[m], m, 1)
