@@ -53,6 +53,22 @@ class Plan:
         scratch = torch.empty(int(lsb[0]), dtype=torch.uint8, device=dev) if lsb[0] > 0 else None
         return cls(order, bins, int(mx[0]), scratch)
 
+    @staticmethod
+    def device_bins_async(offsets: torch.Tensor, stream):
+        """``(order, bins)``, both on the device: the plan order int32[M] and the bin boundaries
+        int64[NBINS + 1] of bce_plan_bins_device_async, enqueued on ``stream`` with no host
+        synchronisation -- for the entries that read the boundaries on the device."""
+        L = N.require_gpu()
+        dev = offsets.device
+        M = offsets.numel() - 1
+        order = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
+        sb = int(L.bce_plan_device_scratch_bytes(M))
+        work = torch.empty(max(sb, 1), dtype=torch.uint8, device=dev)
+        bins = torch.empty(N.NBINS + 1, dtype=torch.int64, device=dev)
+        N.check(L.bce_plan_bins_device_async(N.ptr(offsets), M, N.ptr(order), N.ptr(bins), N.ptr(work), sb, stream),
+                "bce_plan_bins_device_async")
+        return order, bins
+
     @classmethod
     def for_markets(cls, offsets_host: np.ndarray, markets: np.ndarray, device=None) -> "Plan":
         """The plan of a market subset over the FULL CSR (a rank's markets of
@@ -145,13 +161,8 @@ def consensus(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, tabl
     if plan is None and max_len is not None and 64 < max_len <= 4096 and table.n <= (1 << 25):
         # a fresh ragged batch under the caller's bound: planned on the device and launched with
         # no host synchronisation (bce_plan_bins_device_async + bce_consensus_planned_device)
-        order = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-        sb = int(L.bce_plan_device_scratch_bytes(M))
-        work = torch.empty(max(sb, 1), dtype=torch.uint8, device=dev)
-        bins = torch.empty(N.NBINS + 1, dtype=torch.int64, device=dev)
         st = N.stream(dev)
-        N.check(L.bce_plan_bins_device_async(N.ptr(offsets), M, N.ptr(order), N.ptr(bins), N.ptr(work), sb, st),
-                "bce_plan_bins_device_async")
+        order, bins = Plan.device_bins_async(offsets, st)
         N.check(L.bce_consensus_planned_device(*common, N.ptr(order), N.ptr(bins), md, *outs, st),
                 "bce_consensus_planned_device")
         if check:

@@ -14,6 +14,14 @@ from .score import ScorePlan, ScoreResult, score
 HISTORY_MAX_LEN = 4096  # the longest market the history kernels take (the wide kernels' limit)
 
 
+def _alloc_per_signal(n_signals: int, device):
+    """The four uninitialised per-signal arrays (fp64 x 3, int32) of a per-signal result."""
+    f64 = dict(dtype=torch.float64, device=device)
+    n = max(int(n_signals), 1)
+    return (torch.empty(n, **f64)[:n_signals], torch.empty(n, **f64)[:n_signals],
+            torch.empty(n, **f64)[:n_signals], torch.empty(n, dtype=torch.int32, device=device)[:n_signals])
+
+
 @dataclass
 class HistoryResult:
     """:func:`consensus_history`: one point per signal, at the signal's CSR position.  Point k of
@@ -27,10 +35,7 @@ class HistoryResult:
     @classmethod
     def alloc(cls, n_signals: int, device) -> "HistoryResult":
         """Uninitialised outputs for ``n_signals`` points."""
-        f64 = dict(dtype=torch.float64, device=device)
-        n = max(int(n_signals), 1)
-        return cls(torch.empty(n, **f64)[:n_signals], torch.empty(n, **f64)[:n_signals],
-                   torch.empty(n, **f64)[:n_signals], torch.empty(n, dtype=torch.int32, device=device)[:n_signals])
+        return cls(*_alloc_per_signal(n_signals, device))
 
     def is_null(self) -> torch.Tensor:
         """bool[N]: consensus is None at the point (total weight == 0, core.py:131)."""
@@ -53,9 +58,56 @@ class HistoryResult:
                                pick(self.n_unique), None, None, None, None)
 
 
-def _too_long(market: int, n: int) -> ValueError:
-    return ValueError(f"consensus_history: market {market} has {n} signals; the longest market it takes has "
-                      f"{HISTORY_MAX_LEN}")
+def _per_signal(name: str, entry: str, offsets, sid, prob, table, outputs, plan, max_len, offsets_host, check):
+    """The routes :func:`consensus_history` and :func:`leave_one_out` share (documented there):
+    validates ``max_len``, refuses a market over ``HISTORY_MAX_LEN`` signals where the host knows
+    the lengths (a ``ValueError`` that starts with ``name``), picks the route, calls ``entry`` and
+    checks its status.  ``outputs(M, Nsig, dev)`` is called once the arguments have passed and
+    returns the result, whose four per-signal arrays the entry takes, and the pointers the entry
+    takes behind them; the result is returned."""
+    def too_long(market: int, n: int) -> ValueError:
+        return ValueError(f"{name}: market {market} has {n} signals; the longest market it takes has "
+                          f"{HISTORY_MAX_LEN}")
+
+    if max_len is not None and not 0 < int(max_len) <= HISTORY_MAX_LEN:
+        raise ValueError(f"max_len must be in [1, {HISTORY_MAX_LEN}] (got {max_len})")
+    if offsets_host is not None:
+        lens = np.diff(np.asarray(offsets_host, np.int64))
+        if lens.size and int(lens.max()) > HISTORY_MAX_LEN:
+            m = int(np.argmax(lens > HISTORY_MAX_LEN))
+            raise too_long(m, int(lens[m]))
+        if plan is None and max_len is None:
+            max_len = max(int(lens.max(initial=0)), 1)
+            if max_len > 64:
+                plan = Plan.build(offsets_host, offsets.device)
+    M = offsets.numel() - 1
+    Nsig = sid.numel()
+    dev = offsets.device
+    call = getattr(N.require_gpu(), entry)
+    if plan is None and max_len is None:
+        plan = Plan.build_device(offsets)
+    if plan is not None:
+        b = plan.bin_start
+        if b[N.NBINS] > b[N.NBINS - 1]:
+            m = int(plan.order[int(b[N.NBINS - 1])])
+            raise too_long(m, int(offsets[m + 1] - offsets[m]))
+    res, more = outputs(M, Nsig, dev)
+    common = (N.ptr(offsets), M, N.ptr(sid), N.ptr(prob), Nsig, N.ptr(table.relconf), N.ptr(table.bits), table.n)
+    outs = (N.ptr(res.consensus), N.ptr(res.confidence), N.ptr(res.total_weight), N.ptr(res.n_unique), *more)
+    st = N.stream(dev)
+    null = N.ptr(None)
+    if plan is not None:
+        rc = call(*common, N.ptr(plan.order), int(plan.bin_start[N.NBINS]),
+                  N.ptr(np.ascontiguousarray(plan.bin_start, np.int64)), null, 0, *outs, st)
+    elif max_len <= 64:
+        rc = call(*common, null, 0, null, null, int(max_len), *outs, st)
+    else:  # planned on the device under the caller's bound: no host synchronisation
+        order, bins = Plan.device_bins_async(offsets, st)
+        rc = call(*common, N.ptr(order), M, null, N.ptr(bins), 0, *outs, st)
+    N.check(rc, entry)
+    if check:
+        N.check_faults(dev, name)
+    return res
 
 
 def consensus_history(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, table: SourceTable, *,
@@ -80,50 +132,9 @@ def consensus_history(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tens
     raises the device fault word, as does a market longer than a ``max_len <= 64`` bound and a
     ``sid`` outside ``[0, table.n)`` (its row read clamped).  ``check=True`` synchronises and
     raises :class:`BCEError` for those.  Positions left untouched hold what ``out`` held."""
-    if max_len is not None and not 0 < int(max_len) <= HISTORY_MAX_LEN:
-        raise ValueError(f"max_len must be in [1, {HISTORY_MAX_LEN}] (got {max_len})")
-    if offsets_host is not None:
-        lens = np.diff(np.asarray(offsets_host, np.int64))
-        if lens.size and int(lens.max()) > HISTORY_MAX_LEN:
-            m = int(np.argmax(lens > HISTORY_MAX_LEN))
-            raise _too_long(m, int(lens[m]))
-        if plan is None and max_len is None:
-            max_len = max(int(lens.max(initial=0)), 1)
-            if max_len > 64:
-                plan = Plan.build(offsets_host, offsets.device)
-    M = offsets.numel() - 1
-    Nsig = sid.numel()
-    dev = offsets.device
-    L = N.require_gpu()
-    if plan is None and max_len is None:
-        plan = Plan.build_device(offsets)
-    if plan is not None:
-        b = plan.bin_start
-        if b[N.NBINS] > b[N.NBINS - 1]:
-            m = int(plan.order[int(b[N.NBINS - 1])])
-            raise _too_long(m, int(offsets[m + 1] - offsets[m]))
-    res = out or HistoryResult.alloc(Nsig, dev)
-    common = (N.ptr(offsets), M, N.ptr(sid), N.ptr(prob), Nsig, N.ptr(table.relconf), N.ptr(table.bits), table.n)
-    outs = (N.ptr(res.consensus), N.ptr(res.confidence), N.ptr(res.total_weight), N.ptr(res.n_unique))
-    st = N.stream(dev)
-    null = N.ptr(None)
-    if plan is not None:
-        rc = L.bce_consensus_history(*common, N.ptr(plan.order), int(plan.bin_start[N.NBINS]),
-                                     N.ptr(np.ascontiguousarray(plan.bin_start, np.int64)), null, 0, *outs, st)
-    elif max_len <= 64:
-        rc = L.bce_consensus_history(*common, null, 0, null, null, int(max_len), *outs, st)
-    else:  # planned on the device under the caller's bound: no host synchronisation
-        order = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-        sb = int(L.bce_plan_device_scratch_bytes(M))
-        work = torch.empty(max(sb, 1), dtype=torch.uint8, device=dev)
-        bins = torch.empty(N.NBINS + 1, dtype=torch.int64, device=dev)
-        N.check(L.bce_plan_bins_device_async(N.ptr(offsets), M, N.ptr(order), N.ptr(bins), N.ptr(work), sb, st),
-                "bce_plan_bins_device_async")
-        rc = L.bce_consensus_history(*common, N.ptr(order), M, null, N.ptr(bins), 0, *outs, st)
-    N.check(rc, "bce_consensus_history")
-    if check:
-        N.check_faults(dev, "consensus_history")
-    return res
+    return _per_signal("consensus_history", "bce_consensus_history", offsets, sid, prob, table,
+                       lambda M, Nsig, dev: (out or HistoryResult.alloc(Nsig, dev), ()),
+                       plan, max_len, offsets_host, check)
 
 
 def history_at(offsets: torch.Tensor, arrival_us: torch.Tensor, at_us: torch.Tensor,
@@ -214,6 +225,17 @@ def score_history(hist: HistoryResult, offsets: torch.Tensor, outcome: torch.Ten
     return score(_history_items(offsets, plan), hist.consensus, per_point, valid=~hist.is_null(), **kw)
 
 
+def _walk_entry_table(plan, scopes, offsets: torch.Tensor, prob: torch.Tensor, trace_kwargs) -> SourceTable:
+    """The entry table of a walk-forward plan -- :func:`walk_trace` or, for a
+    :class:`WalkScopePlan`, :func:`walk_scope_trace` ``(plan, *scopes, **trace_kwargs)`` -- after
+    checking that ``offsets`` / ``prob`` are the plan's batch (its entry ids: ``plan.pairs.esid``)."""
+    pp = plan.pairs
+    if offsets.numel() - 1 != pp.n_markets or prob.numel() != pp.esid.numel():
+        raise ValueError("offsets / prob are not the batch the plan was built from")
+    trace = walk_scope_trace if isinstance(plan, WalkScopePlan) else walk_trace
+    return trace(plan, *scopes, **trace_kwargs)[0]
+
+
 def walk_history(plan, *scopes, offsets: torch.Tensor, prob: torch.Tensor, bins: Optional[Plan] = None,
                  max_len: Optional[int] = None, offsets_host: Optional[np.ndarray] = None,
                  out: Optional[HistoryResult] = None, check: bool = False, **trace_kwargs) -> HistoryResult:
@@ -229,10 +251,6 @@ def walk_history(plan, *scopes, offsets: torch.Tensor, prob: torch.Tensor, bins:
     stood at that market's own turn (its forecast time for a lagged plan).  They are not re-read
     at every arrival, so an outcome that resolved between two signals of the same market does not
     move the later points."""
-    pp = plan.pairs
-    if offsets.numel() - 1 != pp.n_markets or prob.numel() != pp.esid.numel():
-        raise ValueError("offsets / prob are not the batch the plan was built from")
-    trace = walk_scope_trace if isinstance(plan, WalkScopePlan) else walk_trace
-    wtable = trace(plan, *scopes, **trace_kwargs)[0]
-    return consensus_history(offsets, pp.esid, prob.to(torch.float64), wtable, plan=bins, max_len=max_len,
+    wtable = _walk_entry_table(plan, scopes, offsets, prob, trace_kwargs)
+    return consensus_history(offsets, plan.pairs.esid, prob.to(torch.float64), wtable, plan=bins, max_len=max_len,
                              offsets_host=offsets_host, out=out, check=check)

@@ -8,9 +8,8 @@ import torch
 from .. import _native as N
 from .tables import SourceTable, _check_csr
 from .consensus import ConsensusResult, Plan, _alloc
-from .walk import WalkScopePlan, walk_scope_trace, walk_trace
 from .score import ScorePlan, ScoreResult, _score_segments, score
-from .history import HISTORY_MAX_LEN, _market_of_point
+from .history import _alloc_per_signal, _market_of_point, _per_signal, _walk_entry_table
 
 
 @dataclass
@@ -28,12 +27,8 @@ class LeaveOneOutResult:
     @classmethod
     def alloc(cls, n_signals: int, device, n_markets: Optional[int] = None) -> "LeaveOneOutResult":
         """Uninitialised outputs for ``n_signals`` signals; with ``n_markets``, ``full`` too."""
-        f64 = dict(dtype=torch.float64, device=device)
-        n = max(int(n_signals), 1)
         full = None if n_markets is None else _alloc(int(n_markets), 0, device, False, False)
-        return cls(torch.empty(n, **f64)[:n_signals], torch.empty(n, **f64)[:n_signals],
-                   torch.empty(n, **f64)[:n_signals], torch.empty(n, dtype=torch.int32, device=device)[:n_signals],
-                   full)
+        return cls(*_alloc_per_signal(n_signals, device), full)
 
     def is_null(self) -> torch.Tensor:
         """bool[N]: the consensus without the source is None -- nothing is left, or what is left
@@ -51,11 +46,6 @@ class LeaveOneOutResult:
         null = self.is_null() | full.is_null(offsets)[market]
         nan = torch.full_like(self.consensus, float("nan"))
         return torch.where(null, nan, full.consensus[market] - self.consensus)
-
-
-def _too_long(market: int, n: int) -> ValueError:
-    return ValueError(f"leave_one_out: market {market} has {n} signals; the longest market it takes has "
-                      f"{HISTORY_MAX_LEN}")
 
 
 def leave_one_out(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, table: SourceTable, *,
@@ -81,55 +71,16 @@ def leave_one_out(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tensor, 
     when the host knows the lengths, else it is left untouched and raises the device fault word,
     as does a market over a ``max_len <= 64`` bound and a ``sid`` outside ``[0, table.n)`` (its
     row read clamped).  ``check=True`` synchronises and raises :class:`BCEError` for those."""
-    if max_len is not None and not 0 < int(max_len) <= HISTORY_MAX_LEN:
-        raise ValueError(f"max_len must be in [1, {HISTORY_MAX_LEN}] (got {max_len})")
-    if offsets_host is not None:
-        lens = np.diff(np.asarray(offsets_host, np.int64))
-        if lens.size and int(lens.max()) > HISTORY_MAX_LEN:
-            m = int(np.argmax(lens > HISTORY_MAX_LEN))
-            raise _too_long(m, int(lens[m]))
-        if plan is None and max_len is None:
-            max_len = max(int(lens.max(initial=0)), 1)
-            if max_len > 64:
-                plan = Plan.build(offsets_host, offsets.device)
-    M = offsets.numel() - 1
-    Nsig = sid.numel()
-    dev = offsets.device
-    L = N.require_gpu()
-    if plan is None and max_len is None:
-        plan = Plan.build_device(offsets)
-    if plan is not None:
-        b = plan.bin_start
-        if b[N.NBINS] > b[N.NBINS - 1]:
-            m = int(plan.order[int(b[N.NBINS - 1])])
-            raise _too_long(m, int(offsets[m + 1] - offsets[m]))
-    res = out or LeaveOneOutResult.alloc(Nsig, dev)
-    if full and res.full is None:
-        res.full = _alloc(M, 0, dev, False, False)
-    fr = res.full if full else None
-    common = (N.ptr(offsets), M, N.ptr(sid), N.ptr(prob), Nsig, N.ptr(table.relconf), N.ptr(table.bits), table.n)
-    outs = (N.ptr(res.consensus), N.ptr(res.confidence), N.ptr(res.total_weight), N.ptr(res.n_unique),
-            N.ptr(fr.consensus if fr else None), N.ptr(fr.confidence if fr else None),
-            N.ptr(fr.total_weight if fr else None), N.ptr(fr.n_unique if fr else None))
-    st = N.stream(dev)
-    null = N.ptr(None)
-    if plan is not None:
-        rc = L.bce_consensus_leave_one_out(*common, N.ptr(plan.order), int(plan.bin_start[N.NBINS]),
-                                           N.ptr(np.ascontiguousarray(plan.bin_start, np.int64)), null, 0, *outs, st)
-    elif max_len <= 64:
-        rc = L.bce_consensus_leave_one_out(*common, null, 0, null, null, int(max_len), *outs, st)
-    else:  # planned on the device under the caller's bound: no host synchronisation
-        order = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-        sb = int(L.bce_plan_device_scratch_bytes(M))
-        work = torch.empty(max(sb, 1), dtype=torch.uint8, device=dev)
-        bins = torch.empty(N.NBINS + 1, dtype=torch.int64, device=dev)
-        N.check(L.bce_plan_bins_device_async(N.ptr(offsets), M, N.ptr(order), N.ptr(bins), N.ptr(work), sb, st),
-                "bce_plan_bins_device_async")
-        rc = L.bce_consensus_leave_one_out(*common, N.ptr(order), M, null, N.ptr(bins), 0, *outs, st)
-    N.check(rc, "bce_consensus_leave_one_out")
-    if check:
-        N.check_faults(dev, "leave_one_out")
-    return res
+    def outputs(M, Nsig, dev):
+        res = out or LeaveOneOutResult.alloc(Nsig, dev)
+        if full and res.full is None:
+            res.full = _alloc(M, 0, dev, False, False)
+        fr = res.full if full else None
+        return res, (N.ptr(fr.consensus if fr else None), N.ptr(fr.confidence if fr else None),
+                     N.ptr(fr.total_weight if fr else None), N.ptr(fr.n_unique if fr else None))
+
+    return _per_signal("leave_one_out", "bce_consensus_leave_one_out", offsets, sid, prob, table, outputs,
+                       plan, max_len, offsets_host, check)
 
 
 def _loo_items(offsets: torch.Tensor, sid: torch.Tensor, n_sources: int, per: str = "pair") -> ScorePlan:
@@ -190,10 +141,6 @@ def walk_leave_one_out(plan, *scopes, offsets: torch.Tensor, prob: torch.Tensor,
     the entry table with the plan's entry ids; ``bins`` is its length-bin :class:`Plan`.  Every
     market is read with the reliabilities as they stood at its own turn.  Nothing is committed;
     ``full`` equals ``walk_forward(commit=False)``."""
-    pp = plan.pairs
-    if offsets.numel() - 1 != pp.n_markets or prob.numel() != pp.esid.numel():
-        raise ValueError("offsets / prob are not the batch the plan was built from")
-    trace = walk_scope_trace if isinstance(plan, WalkScopePlan) else walk_trace
-    wtable = trace(plan, *scopes, **trace_kwargs)[0]
-    return leave_one_out(offsets, pp.esid, prob.to(torch.float64), wtable, plan=bins, max_len=max_len,
+    wtable = _walk_entry_table(plan, scopes, offsets, prob, trace_kwargs)
+    return leave_one_out(offsets, plan.pairs.esid, prob.to(torch.float64), wtable, plan=bins, max_len=max_len,
                          offsets_host=offsets_host, out=out, full=full, check=check)

@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "consensus_common.hpp"
+#include "consensus_sorted.hpp"
 #include "plan_host.hpp"
 
 #pragma clang fp contract(off)
@@ -317,9 +318,11 @@ __device__ __forceinline__ double block_sum_tree(double v, double* red) {
 
 // Pass structure per market (all arrays length P = next pow2 >= n):
 //   0  keys[t] = sid<<32 | t, Pr[t] = prob (input order); first out-of-range index
-//   1  bitonic sort of keys (ascending sid, then input index == core.py:103,115)
+//   1  bitonic sort of keys (ascending sid, then input index == core.py:103,115;
+//      block_bitonic_sort_u64, consensus_sorted.hpp)
 //   2  leaders (first position of each sid run) sum their run's probabilities in input
-//      order (core.py:116), compact index j by block scan -> Av[j] = avg, Sj[j] = sid
+//      order (core.py:116), compact index j by block scan (block_compact_index) ->
+//      Av[j] = avg, Sj[j] = sid
 //   3  per unique j: w = rel, W[j] = w, A[j] = avg*w, C[j] = conf*w, per-unique outputs
 //   4  ordered sums over j (exact: one lane per chain; fast: fixed tree)
 //   5  normalizedWeight[j] = W[j] / total
@@ -339,7 +342,6 @@ __global__ __launch_bounds__(kLongThreads) void consensus_long_kernel(ConsArgs a
   const int tid = threadIdx.x;
   const int lane = lane_id();
   const int wv = tid / kWave;
-  const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
 
   for (int64_t li = blockIdx.x; li < a.n_list; li += gridDim.x) {
     const int32_t m = a.list ? a.list[li] : (int32_t)li;
@@ -386,21 +388,7 @@ __global__ __launch_bounds__(kLongThreads) void consensus_long_kernel(ConsArgs a
     const int errv = sInt[0];
 
     // ---- pass 1: bitonic sort ----------------------------------------------------------
-    for (int k = 2; k <= P; k <<= 1) {
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int c = tid; c < (P >> 1); c += NT) {
-          const int lo = ((c & ~(j - 1)) << 1) | (c & (j - 1));
-          const int hi = lo | j;
-          const bool up = (lo & k) == 0;
-          const unsigned long long x = keys[lo], y = keys[hi];
-          if ((x > y) == up) {
-            keys[lo] = y;
-            keys[hi] = x;
-          }
-        }
-        __syncthreads();
-      }
-    }
+    block_bitonic_sort_u64(keys, P, tid, NT);
 
     // ---- pass 2: leaders, run sums in input order, compact index ------------------------
     int u = 0;
@@ -424,22 +412,11 @@ __global__ __launch_bounds__(kLongThreads) void consensus_long_kernel(ConsArgs a
           avg = (cnt > 1) ? s / (double)cnt : s;
         }
       }
-      const unsigned long long bm = ballot(first);
-      if (lane == 0) sInt[2 + wv] = __popcll(bm);
-      __syncthreads();
-      int before = u, chunk = 0;
-#pragma unroll
-      for (int q = 0; q < NW; ++q) {
-        const int cq = sInt[2 + q];
-        if (q < wv) before += cq;
-        chunk += cq;
-      }
+      const int j = block_compact_index(first, sInt + 2, wv, NW, lane, u);
       if (first) {
-        const int j = before + __popcll(bm & below);
         Cv[j] = avg;
         Sj[j] = ssid;
       }
-      u += chunk;
       __syncthreads();
     }
 
@@ -510,19 +487,6 @@ __global__ __launch_bounds__(kLongThreads) void consensus_long_kernel(ConsArgs a
 // host launchers
 // ======================================================================================
 namespace bce {
-
-// A persistent grid: min(units, CUs x workgroups per CU) workgroups, all resident at once,
-// the units (tiles) dealt round-robin inside the kernel.  `fallback`: workgroups per CU when
-// the occupancy query fails.
-int launch_persistent(void (*kernel)(ConsArgs), int threads, int fallback, int64_t units, const char* name,
-                      const ConsArgs& a, hipStream_t st) {
-  if (units == 0) return BCE_OK;
-  const int per_cu = blocks_per_cu(reinterpret_cast<const void*>(kernel), threads, 0, fallback, name);
-  const int64_t cap = (int64_t)cu_count() * per_cu;
-  const int grid = (int)(units < cap ? units : cap);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, st, a);
-  return check_launch(name);
-}
 
 namespace {
 

@@ -4,9 +4,11 @@
 // consensus_lane.hpp; consensus_tab.hip: the LDS-table kernel for contiguous short markets;
 // consensus_wide.hip: 64 < n <= 4096, its sort network in wide_sort.hpp and its chain loops in
 // ordered_chain.hpp; consensus_history.hip: every market's consensus after each signal;
-// consensus_leave_one_out.hip: every market's consensus without each of its sources;
-// consensus_api.hip: the C entries that pick among them; plan.hip: the planners), and the few
-// device pieces every one of them writes the same way.
+// consensus_leave_one_out.hip: every market's consensus without each of its sources -- what
+// these two and consensus_long_kernel share, the sort by (sid, position) first, is
+// consensus_sorted.hpp; consensus_api.hip: the C entries that pick among them; plan.hip: the
+// planners), and the few device pieces and the persistent launch every one of them writes the
+// same way.
 #pragma once
 #pragma clang fp contract(off)
 
@@ -82,13 +84,17 @@ __device__ __forceinline__ bool is_present(const uint32_t* bits, int s) {
 // ---- results every consensus kernel writes the same way ------------------------------------
 // the four per-market values (core.py:131-133: no weight, no consensus); err_idx stays with
 // the caller
+__device__ __forceinline__ void store_row(double* consensus, double* confidence, double* total_weight,
+                                          int32_t* n_unique, int64_t at, double total, double ws, double cs, int j) {
+  const bool null_ = (total == 0.0);
+  consensus[at] = null_ ? 0.0 : ws / total;
+  confidence[at] = null_ ? 0.0 : cs / total;
+  total_weight[at] = total;
+  n_unique[at] = j;
+}
 __device__ __forceinline__ void store_market(const ConsArgs& a, int64_t mk, double total, double ws, double cs,
                                              int j) {
-  const bool null_ = (total == 0.0);
-  a.consensus[mk] = null_ ? 0.0 : ws / total;
-  a.confidence[mk] = null_ ? 0.0 : cs / total;
-  a.total_weight[mk] = total;
-  a.n_unique[mk] = j;
+  store_row(a.consensus, a.confidence, a.total_weight, a.n_unique, mk, total, ws, cs, j);
 }
 // bit 31 of usid: the source is not a key of the reliability dict (core.py:167-170); `word` is
 // the present word of sid
@@ -220,10 +226,24 @@ int launch_tab32(const ConsArgs& a, hipStream_t st);
 int launch_seg_for_len(int max_len, const ConsArgs& a, hipStream_t st);
 int launch_long_lds(const ConsArgs& a, hipStream_t st);
 int launch_long_global(ConsArgs a, void* scratch, int64_t stride, hipStream_t st);
-// ... and the persistent launch its short-market kernels and the lane kernels share: a grid of
-// min(units, resident workgroups), `fallback` workgroups per CU if the occupancy query fails.
-int launch_persistent(void (*kernel)(ConsArgs), int threads, int fallback, int64_t units, const char* name,
-                      const ConsArgs& a, hipStream_t st);
+// ... and the persistent launch the short-market kernels of every translation unit share: a grid
+// of min(units, CUs x resident workgroups per CU) workgroups, all resident at once, the units
+// (tiles, rounds) dealt round-robin inside the kernel; `fallback` workgroups per CU if the
+// occupancy query fails.  The kernel takes `args...`; most take the ConsArgs alone.
+template <class... KA, class... A>
+int launch_persistent(void (*kernel)(KA...), int threads, int fallback, int64_t units, const char* name,
+                      hipStream_t st, const A&... args) {
+  if (units == 0) return BCE_OK;
+  const int per_cu = blocks_per_cu(reinterpret_cast<const void*>(kernel), threads, 0, fallback, name);
+  const int64_t cap = (int64_t)cu_count() * per_cu;
+  const int grid = (int)(units < cap ? units : cap);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, st, args...);
+  return check_launch(name);
+}
+inline int launch_persistent(void (*kernel)(ConsArgs), int threads, int fallback, int64_t units, const char* name,
+                             const ConsArgs& a, hipStream_t st) {
+  return launch_persistent(kernel, threads, fallback, units, name, st, a);
+}
 inline int64_t ceil_div(int64_t n, int64_t d) { return (n + d - 1) / d; }
 
 // consensus_lane.hip: the lane-per-market kernels for n <= G in {8, 16, 32}: market lists (lpm),

@@ -18,14 +18,18 @@
 //                           bitonic sort of consensus_long_kernel in LDS (32 B per signal: 128 KiB
 //                           at 4096), thread t takes points t, t + blockDim, ...
 //
+// This file holds what only the history does: history_point, the walk of one point, and what the
+// two kernels stage for it.  The market claim, the loads and the rank of the short kernel, the
+// claim, the key fill and the sort of the long one, the launchers and the body of the C entry are
+// consensus_sorted.hpp's, shared with consensus_leave_one_out.hip.
+//
 // The work is QUADRATIC in the market length by construction: n points of n steps each, 16.8M
 // steps for a 4096-signal market, spread over the workgroup.  Markets longer than 4096 signals
 // are left untouched and raise kFaultTooLong.  A sid outside [0, n_sources) has its row read
 // clamped and raises kFaultSid.  Keys are 64 bits wide ((sid << 32) | position): any table size.
 // No floating-point atomics; every output element has exactly one writer.
 #include "consensus_common.hpp"
-#include "consensus_history.hpp"
-#include "plan_host.hpp"
+#include "consensus_sorted.hpp"
 
 #pragma clang fp contract(off)
 
@@ -107,44 +111,14 @@ __global__ __launch_bounds__(64) void history_short_kernel(ConsArgs a) {
   const int64_t n_rounds = (a.n_list + SPR - 1) / SPR;
   bool badsid = false;
   for (int64_t r = blockIdx.x; r < n_rounds; r += gridDim.x) {
-    const int64_t li = r * SPR + lane / G;
-    int64_t off = 0;
-    int n = 0;
-    if (li < a.n_list) {
-      const int64_t m = a.list ? a.list[li] : li;
-      off = a.offsets[m];
-      const int64_t len = a.offsets[m + 1] - off;
-      if (len < 0 || len > G) {  // longer than the launch's bound: report, leave untouched
-        if (a.fault) atomicCAS(a.fault, 0, kFaultTooLong);
-      } else {
-        n = (int)len;
-      }
-    }
-    const bool valid = t < n;
-    unsigned s = 0;
-    double p = 0.0;
-    double2 rc = make_double2(0.0, 0.0);
-    if (valid) {
-      s = hist_row(a.sid[off + t], a.n_sources, badsid);
-      p = a.prob[off + t];
-      rc = hist_gather(a, s);  // core.py:110-112 (cold-start defaults are baked into the table)
-    }
-    sRaw[lane] = s;
-    wave_sync_lds();
-    // rank among the market's unique (sid, position) keys
-    int rank = 0;
-#pragma unroll
-    for (int q = 0; q < G; ++q) {  // no short circuit: every read is issued before the first compare
-      const unsigned sq = sRaw[base + q];
-      rank += (int)((q < n) & ((sq < s) | ((sq == s) & (q < t))));
-    }
-    if (valid) {
-      sKey[base + rank] = ((unsigned long long)s << 32) | (unsigned)t;
-      sProb[base + rank] = p;
-      sRow[base + rank] = rc;
+    const ShortFront f = short_front<G>(a, r, lane, sRaw, badsid);
+    if (f.valid) {
+      sKey[base + f.rank] = ((unsigned long long)f.s << 32) | (unsigned)t;
+      sProb[base + f.rank] = f.p;
+      sRow[base + f.rank] = f.rc;
     }
     wave_sync_lds();
-    if (valid) history_point(a, off + t, sKey + base, sProb + base, sRow + base, n, (unsigned)t);
+    if (f.valid) history_point(a, f.off + t, sKey + base, sProb + base, sRow + base, f.n, (unsigned)t);
     wave_sync_lds();  // the next round overwrites the slots
   }
   if (ballot(badsid)) raise_fault(a.fault, kFaultSid);
@@ -160,45 +134,18 @@ __global__ __launch_bounds__(kHistMaxThreads) void history_long_kernel(ConsArgs 
   double* const prob = reinterpret_cast<double*>(hist_lds + 24 * (size_t)P);
   const int tid = threadIdx.x, NT = blockDim.x;
 
-  // a device-resident plan: its last bin holds the markets longer than 4096, which get no launch
-  if (a.dev_bins && blockIdx.x == 0 && tid == 0 && a.dev_bins[BCE_NBINS] > a.dev_bins[BCE_NBINS - 1] && a.fault)
-    atomicCAS(a.fault, 0, kFaultTooLong);
+  report_plan_too_long(a, tid);
   dev_range(a);
   bool badsid = false;
   for (int64_t li = blockIdx.x; li < a.n_list; li += gridDim.x) {
-    const int64_t m = a.list ? a.list[li] : li;
-    const int64_t off = a.offsets[m];
-    const int64_t len = a.offsets[m + 1] - off;
-    if (len < 0 || len > P) {  // uniform over the workgroup
-      if (tid == 0 && a.fault) atomicCAS(a.fault, 0, kFaultTooLong);
-      continue;
-    }
-    const int n = (int)len;
+    int64_t m, off;
+    int n;
+    if (!claim_market(a, li, P, tid, m, off, n)) continue;
     if (n == 0) continue;
-    int Pm = 64;  // this market's padded size
-    while (Pm < n) Pm <<= 1;
-
-    // ---- keys in arrival order --------------------------------------------------------
-    for (int i = tid; i < Pm; i += NT)
-      key[i] = i < n ? ((unsigned long long)hist_row(a.sid[off + i], a.n_sources, badsid) << 32) | (unsigned)i
-                     : kSent64;
+    // ---- keys in arrival order, sorted by sid, then arrival position ----------------------
+    const int Pm = fill_keys(a, key, off, n, tid, NT, badsid, [](int) {});
     __syncthreads();
-    // ---- bitonic sort: ascending sid, then arrival position (core.py:103,115) -----------
-    for (int k = 2; k <= Pm; k <<= 1) {
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int c = tid; c < (Pm >> 1); c += NT) {
-          const int lo = ((c & ~(j - 1)) << 1) | (c & (j - 1));
-          const int hi = lo | j;
-          const bool up = (lo & k) == 0;
-          const unsigned long long x = key[lo], y = key[hi];
-          if ((x > y) == up) {
-            key[lo] = y;
-            key[hi] = x;
-          }
-        }
-        __syncthreads();
-      }
-    }
+    block_bitonic_sort_u64(key, Pm, tid, NT);
     // ---- probabilities and table rows in sorted order -----------------------------------
     for (int e = tid; e < n; e += NT) {
       const unsigned long long ke = key[e];
@@ -224,22 +171,6 @@ int launch_hist_short(int max_len, const ConsArgs& a, hipStream_t st) {
   }
 }
 
-int launch_hist_long(int64_t max_len, const ConsArgs& a, hipStream_t st) {
-  if (a.n_list == 0) return BCE_OK;
-  int64_t P = next_pow2(max_len < 64 ? 64 : max_len);
-  if (P > kLongMaxLds) P = kLongMaxLds;
-  const int threads = (int)(P < kHistMaxThreads ? P : kHistMaxThreads);
-  const size_t lds = (size_t)kHistElemBytes * (size_t)P;
-  const void* fn = reinterpret_cast<const void*>(&history_long_kernel);
-  const int rc = ensure_dynamic_lds(fn, kHistElemBytes * kLongMaxLds);
-  if (rc) return rc;
-  const int per_cu = blocks_per_cu(fn, threads, lds, 1, "history_long_kernel");
-  const int64_t cap = (int64_t)cu_count() * per_cu;
-  const int grid = (int)(a.n_list < cap ? a.n_list : cap);
-  hipLaunchKernelGGL(history_long_kernel, dim3(grid), dim3(threads), lds, st, a, (int)P);
-  return check_launch("history_long_kernel");
-}
-
 }  // namespace
 }  // namespace bce
 
@@ -252,51 +183,13 @@ extern "C" int bce_consensus_history(const int64_t* offsets, int64_t n_markets, 
                                      int32_t max_len, double* consensus, double* confidence, double* total_weight,
                                      int32_t* n_unique, void* stream) {
   (void)present_bits;  // cold sources already carry their defaults in relconf
-  BCE_REQUIRE(n_markets >= 0 && n_signals >= 0 && n_sources >= 0 && n_list >= 0, "history: negative size");
-  BCE_REQUIRE(max_len >= 0 && max_len <= kLongMaxLds, "history: max_len %d outside [0, %d]", max_len, kLongMaxLds);
-  BCE_REQUIRE(n_markets == 0 || offsets, "history: offsets is NULL");
-  BCE_REQUIRE(n_signals == 0 || (sid && prob), "history: sid/prob NULL");
-  BCE_REQUIRE(n_signals == 0 || (consensus && confidence && total_weight && n_unique),
-              "history: per-point outputs must be non-NULL");
-  BCE_REQUIRE(n_sources == 0 || relconf, "history: source table is NULL");
-  BCE_REQUIRE((uintptr_t)relconf % 16 == 0, "history: relconf must be 16-byte aligned");
-  BCE_REQUIRE(!(bin_start_host && bin_start_dev), "history: one plan, host or device bin boundaries");
-  const bool planned = bin_start_host || bin_start_dev;
-  BCE_REQUIRE(!planned || market_list || n_markets == 0, "history: a plan needs its market order");
-  if (n_markets == 0 || n_signals == 0) return BCE_OK;
-  ConsArgs base{};
-  base.offsets = offsets; base.sid = sid; base.prob = prob;
-  base.relconf = reinterpret_cast<const double2*>(relconf);
-  base.n_sources = n_sources; base.n_signals = n_signals;
-  base.consensus = consensus; base.confidence = confidence; base.total_weight = total_weight;
-  base.n_unique = n_unique;
-  base.fault = fault_word();
   hipStream_t st = as_stream(stream);
-  if (!planned) {  // one launch sized by max_len (0: unknown, as 4096)
-    base.list = market_list;
-    base.n_list = market_list ? n_list : n_markets;
-    if (base.n_list == 0) return BCE_OK;
-    return (max_len > 0 && max_len <= 64) ? launch_hist_short(max_len, base, st)
-                                          : launch_hist_long(max_len > 0 ? max_len : kLongMaxLds, base, st);
-  }
-  // a length-binned plan: one launch per bin, longest bins first; the > 4096 bin runs in the
-  // 4096 launch, which reports its markets and leaves them untouched
-  int rc = BCE_OK;
-  for (int b = BCE_NBINS - 1; b >= 0 && !rc; --b) {
-    if (bin_start_dev && b == BCE_NBINS - 1) continue;  // reported by the long launches
-    ConsArgs a = base;
-    if (bin_start_host) {
-      a.list = market_list + bin_start_host[b];
-      a.n_list = bin_start_host[b + 1] - bin_start_host[b];
-      if (a.n_list == 0) continue;
-    } else {
-      a.list = market_list;    // the whole plan order: the range is read on the device
-      a.n_list = n_markets;    // upper bound: sizes the grid
-      a.dev_bins = bin_start_dev;
-      a.dev_b0 = a.dev_b1 = b;
-    }
-    const int64_t bound = b < BCE_NBINS - 1 ? kBinMax[b] : kLongMaxLds;
-    rc = b <= kPlanSideLast ? launch_hist_short((int)bound, a, st) : launch_hist_long(bound, a, st);
-  }
-  return rc;
+  const PerSignalCall c{offsets, n_markets, sid, prob, n_signals, relconf, n_sources, market_list, n_list,
+                        bin_start_host, bin_start_dev, max_len, consensus, confidence, total_weight, n_unique};
+  return per_signal_launch(
+      "history", "per-point", c, n_markets == 0 || n_signals == 0,
+      [&](int bound, const ConsArgs& a) { return launch_hist_short(bound, a, st); },
+      [&](int64_t bound, const ConsArgs& a) {
+        return launch_market_block(history_long_kernel, kHistElemBytes, bound, a.n_list, "history_long_kernel", st, a);
+      });
 }

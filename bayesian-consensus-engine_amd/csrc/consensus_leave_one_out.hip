@@ -21,12 +21,17 @@
 //                       compacts them; thread t walks leave-outs t, t + blockDim, ... and writes
 //                       the positions of its source's signals.
 //
+// This file holds what only the leave-outs do: loo_walk, the run closing and the compaction into
+// {w, avg * w, conf * w}, and the copy of every leave-out to its source's signals.  The market
+// claim, the loads and the rank of the short kernel, the claim, the key fill, the sort and the
+// compact index of the long one, the launchers and the body of the C entry are
+// consensus_sorted.hpp's, shared with consensus_history.hip.
+//
 // Markets longer than 4096 signals (or than a max_len <= 64 launch takes) are left untouched and
 // raise kFaultTooLong; a sid outside [0, n_sources) has its row read clamped and raises
 // kFaultSid.  No floating-point atomics; every output element has exactly one writer.
 #include "consensus_common.hpp"
-#include "consensus_history.hpp"
-#include "plan_host.hpp"
+#include "consensus_sorted.hpp"
 
 #pragma clang fp contract(off)
 
@@ -42,16 +47,6 @@ struct LooFull {
 };
 
 constexpr int kLooElemBytes = 36;  // LDS per signal of the long kernel (loo_long_kernel)
-
-// core.py:131-144 for one result row (store_market's rule, for any of the two output sets)
-__device__ __forceinline__ void loo_store(double* consensus, double* confidence, double* total_weight,
-                                          int32_t* n_unique, int64_t at, double total, double ws, double cs, int j) {
-  const bool null_ = (total == 0.0);
-  consensus[at] = null_ ? 0.0 : ws / total;
-  confidence[at] = null_ ? 0.0 : cs / total;
-  total_weight[at] = total;
-  n_unique[at] = j;
-}
 
 // Leave-out j of a market's U compact entries: the ordered sums (core.py:120,136,142) over the
 // entries e != j.  The entries come from LDS kLooChunk at a time, read unconditionally ahead of
@@ -103,42 +98,14 @@ __global__ __launch_bounds__(64) void loo_short_kernel(ConsArgs a, LooFull f) {
   const int64_t n_rounds = (a.n_list + SPR - 1) / SPR;
   bool badsid = false;
   for (int64_t r = blockIdx.x; r < n_rounds; r += gridDim.x) {
-    const int64_t li = r * SPR + lane / G;
-    int64_t off = 0, m = -1;  // m >= 0: the market is processed (it may be empty)
-    int n = 0;
-    if (li < a.n_list) {
-      const int64_t mk = a.list ? a.list[li] : li;
-      off = a.offsets[mk];
-      const int64_t len = a.offsets[mk + 1] - off;
-      if (len < 0 || len > G) {  // longer than the launch's bound: report, leave untouched
-        if (a.fault) atomicCAS(a.fault, 0, kFaultTooLong);
-      } else {
-        n = (int)len;
-        m = mk;
-      }
-    }
-    const bool valid = t < n;
-    unsigned s = 0;
-    double p = 0.0;
-    double2 rc = make_double2(0.0, 0.0);
+    const ShortFront sf = short_front<G>(a, r, lane, sRaw, badsid);
+    const int64_t off = sf.off, m = sf.m;  // m >= 0: the market is processed (it may be empty)
+    const int n = sf.n, rank = sf.rank;
+    const bool valid = sf.valid;
     if (valid) {
-      s = hist_row(a.sid[off + t], a.n_sources, badsid);
-      p = a.prob[off + t];
-      rc = hist_gather(a, s);  // core.py:110-112 (cold-start defaults are baked into the table)
-    }
-    sRaw[lane] = s;
-    wave_sync_lds();
-    // rank among the market's unique (sid, position) keys
-    int rank = 0;
-#pragma unroll
-    for (int q = 0; q < G; ++q) {  // no short circuit: every read is issued before the first compare
-      const unsigned sq = sRaw[base + q];
-      rank += (int)((q < n) & ((sq < s) | ((sq == s) & (q < t))));
-    }
-    if (valid) {
-      sSid[base + rank] = s;
-      sProb[base + rank] = p;
-      sRow[base + rank] = rc;
+      sSid[base + rank] = sf.s;
+      sProb[base + rank] = sf.p;
+      sRow[base + rank] = sf.rc;
     }
     wave_sync_lds();
     // lane t now looks at SORTED element t: the first of its source's run is the run's leader
@@ -185,11 +152,11 @@ __global__ __launch_bounds__(64) void loo_short_kernel(ConsArgs a, LooFull f) {
         total += cW[lane];
         ws += cAW[lane];
         cs += cCW[lane];
-        loo_store(f.consensus, f.confidence, f.total_weight, f.n_unique, m, total, ws, cs, U);
+        store_row(f.consensus, f.confidence, f.total_weight, f.n_unique, m, total, ws, cs, U);
       }
     }
     if (m >= 0 && n == 0 && t == 0 && f.consensus)
-      loo_store(f.consensus, f.confidence, f.total_weight, f.n_unique, m, 0.0, 0.0, 0.0, 0);
+      store_row(f.consensus, f.confidence, f.total_weight, f.n_unique, m, 0.0, 0.0, 0.0, 0);
     wave_sync_lds();
     if (valid) {  // consecutive lanes, consecutive addresses; duplicates of a source get copies
       const int64_t at = off + t;
@@ -221,53 +188,23 @@ __global__ __launch_bounds__(kHistMaxThreads) void loo_long_kernel(ConsArgs a, L
   __shared__ int sCnt[kHistMaxThreads / kWave];
   const int tid = threadIdx.x, NT = blockDim.x;
   const int lane = lane_id(), wv = tid / kWave, NW = NT / kWave;
-  const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
 
-  // a device-resident plan: its last bin holds the markets longer than 4096, which get no launch
-  if (a.dev_bins && blockIdx.x == 0 && tid == 0 && a.dev_bins[BCE_NBINS] > a.dev_bins[BCE_NBINS - 1] && a.fault)
-    atomicCAS(a.fault, 0, kFaultTooLong);
+  report_plan_too_long(a, tid);
   dev_range(a);
   bool badsid = false;
   for (int64_t li = blockIdx.x; li < a.n_list; li += gridDim.x) {
-    const int64_t m = a.list ? a.list[li] : li;
-    const int64_t off = a.offsets[m];
-    const int64_t len = a.offsets[m + 1] - off;
-    if (len < 0 || len > P) {  // uniform over the workgroup
-      if (tid == 0 && a.fault) atomicCAS(a.fault, 0, kFaultTooLong);
-      continue;
-    }
-    const int n = (int)len;
+    int64_t m, off;
+    int n;
+    if (!claim_market(a, li, P, tid, m, off, n)) continue;
     if (n == 0) {
       if (tid == 0 && f.consensus)
-        loo_store(f.consensus, f.confidence, f.total_weight, f.n_unique, m, 0.0, 0.0, 0.0, 0);
+        store_row(f.consensus, f.confidence, f.total_weight, f.n_unique, m, 0.0, 0.0, 0.0, 0);
       continue;
     }
-    int Pm = 64;  // this market's padded size
-    while (Pm < n) Pm <<= 1;
-
-    // ---- keys and probabilities in arrival order ---------------------------------------
-    for (int i = tid; i < Pm; i += NT) {
-      key[i] = i < n ? ((unsigned long long)hist_row(a.sid[off + i], a.n_sources, badsid) << 32) | (unsigned)i
-                     : kSent64;
-      if (i < n) Pr[i] = a.prob[off + i];
-    }
+    // ---- keys and probabilities in arrival order, the keys then sorted by sid, then position
+    const int Pm = fill_keys(a, key, off, n, tid, NT, badsid, [&](int i) { Pr[i] = a.prob[off + i]; });
     __syncthreads();
-    // ---- bitonic sort: ascending sid, then arrival position (core.py:103,115) -----------
-    for (int k = 2; k <= Pm; k <<= 1) {
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int c = tid; c < (Pm >> 1); c += NT) {
-          const int lo = ((c & ~(j - 1)) << 1) | (c & (j - 1));
-          const int hi = lo | j;
-          const bool up = (lo & k) == 0;
-          const unsigned long long x = key[lo], y = key[hi];
-          if ((x > y) == up) {
-            key[lo] = y;
-            key[hi] = x;
-          }
-        }
-        __syncthreads();
-      }
-    }
+    block_bitonic_sort_u64(key, Pm, tid, NT);
     // ---- the leaders (first sorted element of a source's run), before the keys are overwritten
     unsigned leads = 0;  // bit c: sorted element c * NT + tid leads a run
     for (int c0 = 0, c = 0; c0 < n; c0 += NT, ++c) {
@@ -305,24 +242,14 @@ __global__ __launch_bounds__(kHistMaxThreads) void loo_long_kernel(ConsArgs a, L
           cw = row.y * row.x;  // core.py:142
         }
       }
-      const unsigned long long bm = ballot(first);
-      if (lane == 0) sCnt[wv] = __popcll(bm);
-      __syncthreads();
-      int before = U, pass = 0;
-      for (int q = 0; q < NW; ++q) {
-        const int cq = sCnt[q];
-        if (q < wv) before += cq;
-        pass += cq;
-      }
+      const int j = block_compact_index(first, sCnt, wv, NW, lane, U);
       if (e < n) sPos[e] = (unsigned short)pos;
       if (first) {
-        const int j = before + __popcll(bm & below);
         W[j] = w;
         AW[j] = aw;
         CW[j] = cw;
         rStart[j] = (unsigned short)e;
       }
-      U += pass;
       __syncthreads();
     }
     // ---- the leave-outs ------------------------------------------------------------------------
@@ -343,7 +270,7 @@ __global__ __launch_bounds__(kHistMaxThreads) void loo_long_kernel(ConsArgs a, L
         total += W[j];
         ws += AW[j];
         cs += CW[j];
-        loo_store(f.consensus, f.confidence, f.total_weight, f.n_unique, m, total, ws, cs, U);
+        store_row(f.consensus, f.confidence, f.total_weight, f.n_unique, m, total, ws, cs, U);
       }
     }
     __syncthreads();  // the next market overwrites the LDS
@@ -351,38 +278,15 @@ __global__ __launch_bounds__(kHistMaxThreads) void loo_long_kernel(ConsArgs a, L
   if (ballot(badsid)) raise_fault(a.fault, kFaultSid);
 }
 
-template <int G>
-int launch_loo_short_g(const ConsArgs& a, const LooFull& f, hipStream_t st, const char* name) {
-  const int64_t rounds = ceil_div(a.n_list, kWave / G);
-  if (rounds == 0) return BCE_OK;
-  const int per_cu = blocks_per_cu(reinterpret_cast<const void*>(&loo_short_kernel<G>), 64, 0, 8, name);
-  const int64_t cap = (int64_t)cu_count() * per_cu;
-  const int grid = (int)(rounds < cap ? rounds : cap);
-  hipLaunchKernelGGL(loo_short_kernel<G>, dim3(grid), dim3(64), 0, st, a, f);
-  return check_launch(name);
-}
-
 int launch_loo_short(int max_len, const ConsArgs& a, const LooFull& f, hipStream_t st) {
-  if (max_len <= 8) return launch_loo_short_g<8>(a, f, st, "loo_short_kernel<8>");
-  if (max_len <= 16) return launch_loo_short_g<16>(a, f, st, "loo_short_kernel<16>");
-  if (max_len <= 32) return launch_loo_short_g<32>(a, f, st, "loo_short_kernel<32>");
-  return launch_loo_short_g<64>(a, f, st, "loo_short_kernel<64>");
-}
-
-int launch_loo_long(int64_t max_len, const ConsArgs& a, const LooFull& f, hipStream_t st) {
-  if (a.n_list == 0) return BCE_OK;
-  int64_t P = next_pow2(max_len < 64 ? 64 : max_len);
-  if (P > kLongMaxLds) P = kLongMaxLds;
-  const int threads = (int)(P < kHistMaxThreads ? P : kHistMaxThreads);
-  const size_t lds = (size_t)kLooElemBytes * (size_t)P;
-  const void* fn = reinterpret_cast<const void*>(&loo_long_kernel);
-  const int rc = ensure_dynamic_lds(fn, kLooElemBytes * kLongMaxLds);
-  if (rc) return rc;
-  const int per_cu = blocks_per_cu(fn, threads, lds, 1, "loo_long_kernel");
-  const int64_t cap = (int64_t)cu_count() * per_cu;
-  const int grid = (int)(a.n_list < cap ? a.n_list : cap);
-  hipLaunchKernelGGL(loo_long_kernel, dim3(grid), dim3(threads), lds, st, a, f, (int)P);
-  return check_launch("loo_long_kernel");
+  const int G = max_len <= 8 ? 8 : max_len <= 16 ? 16 : max_len <= 32 ? 32 : 64;
+  const int64_t rounds = ceil_div(a.n_list, kWave / G);
+  switch (G) {
+    case 8: return launch_persistent(loo_short_kernel<8>, 64, 8, rounds, "loo_short_kernel<8>", st, a, f);
+    case 16: return launch_persistent(loo_short_kernel<16>, 64, 8, rounds, "loo_short_kernel<16>", st, a, f);
+    case 32: return launch_persistent(loo_short_kernel<32>, 64, 8, rounds, "loo_short_kernel<32>", st, a, f);
+    default: return launch_persistent(loo_short_kernel<64>, 64, 8, rounds, "loo_short_kernel<64>", st, a, f);
+  }
 }
 
 }  // namespace
@@ -400,57 +304,18 @@ extern "C" int bce_consensus_leave_one_out(const int64_t* offsets, int64_t n_mar
                                            double* full_confidence, double* full_total_weight,
                                            int32_t* full_n_unique, void* stream) {
   (void)present_bits;  // cold sources already carry their defaults in relconf
-  BCE_REQUIRE(n_markets >= 0 && n_signals >= 0 && n_sources >= 0 && n_list >= 0, "leave_one_out: negative size");
-  BCE_REQUIRE(max_len >= 0 && max_len <= kLongMaxLds, "leave_one_out: max_len %d outside [0, %d]", max_len,
-              kLongMaxLds);
-  BCE_REQUIRE(n_markets == 0 || offsets, "leave_one_out: offsets is NULL");
-  BCE_REQUIRE(n_signals == 0 || (sid && prob), "leave_one_out: sid/prob NULL");
-  BCE_REQUIRE(n_signals == 0 || (consensus && confidence && total_weight && n_unique),
-              "leave_one_out: per-signal outputs must be non-NULL");
   const int n_full = (full_consensus != nullptr) + (full_confidence != nullptr) + (full_total_weight != nullptr) +
                      (full_n_unique != nullptr);
   BCE_REQUIRE(n_full == 0 || n_full == 4, "leave_one_out: the full_* outputs are all NULL or all non-NULL");
-  BCE_REQUIRE(n_sources == 0 || relconf, "leave_one_out: source table is NULL");
-  BCE_REQUIRE((uintptr_t)relconf % 16 == 0, "leave_one_out: relconf must be 16-byte aligned");
-  BCE_REQUIRE(!(bin_start_host && bin_start_dev), "leave_one_out: one plan, host or device bin boundaries");
-  const bool planned = bin_start_host || bin_start_dev;
-  BCE_REQUIRE(!planned || market_list || n_markets == 0, "leave_one_out: a plan needs its market order");
-  // without signals every market is empty: only the full_* rows (zeros) are left to write
-  if (n_markets == 0 || (n_signals == 0 && n_full == 0)) return BCE_OK;
-  ConsArgs base{};
-  base.offsets = offsets; base.sid = sid; base.prob = prob;
-  base.relconf = reinterpret_cast<const double2*>(relconf);
-  base.n_sources = n_sources; base.n_signals = n_signals;
-  base.consensus = consensus; base.confidence = confidence; base.total_weight = total_weight;
-  base.n_unique = n_unique;
-  base.fault = fault_word();
   const LooFull full{full_consensus, full_confidence, full_total_weight, full_n_unique};
   hipStream_t st = as_stream(stream);
-  if (!planned) {  // one launch sized by max_len (0: unknown, as 4096)
-    base.list = market_list;
-    base.n_list = market_list ? n_list : n_markets;
-    if (base.n_list == 0) return BCE_OK;
-    return (max_len > 0 && max_len <= 64) ? launch_loo_short(max_len, base, full, st)
-                                          : launch_loo_long(max_len > 0 ? max_len : kLongMaxLds, base, full, st);
-  }
-  // a length-binned plan: one launch per bin, longest bins first; the > 4096 bin runs in the
-  // 4096 launch, which reports its markets and leaves them untouched
-  int rc = BCE_OK;
-  for (int b = BCE_NBINS - 1; b >= 0 && !rc; --b) {
-    if (bin_start_dev && b == BCE_NBINS - 1) continue;  // reported by the long launches
-    ConsArgs a = base;
-    if (bin_start_host) {
-      a.list = market_list + bin_start_host[b];
-      a.n_list = bin_start_host[b + 1] - bin_start_host[b];
-      if (a.n_list == 0) continue;
-    } else {
-      a.list = market_list;    // the whole plan order: the range is read on the device
-      a.n_list = n_markets;    // upper bound: sizes the grid
-      a.dev_bins = bin_start_dev;
-      a.dev_b0 = a.dev_b1 = b;
-    }
-    const int64_t bound = b < BCE_NBINS - 1 ? kBinMax[b] : kLongMaxLds;
-    rc = b <= kPlanSideLast ? launch_loo_short((int)bound, a, full, st) : launch_loo_long(bound, a, full, st);
-  }
-  return rc;
+  const PerSignalCall c{offsets, n_markets, sid, prob, n_signals, relconf, n_sources, market_list, n_list,
+                        bin_start_host, bin_start_dev, max_len, consensus, confidence, total_weight, n_unique};
+  // without signals every market is empty: only the full_* rows (zeros) are left to write
+  return per_signal_launch(
+      "leave_one_out", "per-signal", c, n_markets == 0 || (n_signals == 0 && n_full == 0),
+      [&](int bound, const ConsArgs& a) { return launch_loo_short(bound, a, full, st); },
+      [&](int64_t bound, const ConsArgs& a) {
+        return launch_market_block(loo_long_kernel, kLooElemBytes, bound, a.n_list, "loo_long_kernel", st, a, full);
+      });
 }

@@ -332,6 +332,42 @@ def test_too_long_markets_and_bad_sids_are_reported():
     N.check_faults(_dev(), "fault word is cleared")
 
 
+# G lanes per market: the first 64 / G markets share the first wave; the too-long one is not its first
+SAME_WAVE_LENS = {8: (5, 8, 9, 3, 0, 1, 8, 7, 2, 8, 6, 4), 16: (16, 17, 0, 9, 1, 16, 12, 3, 15, 2, 16, 8)}
+
+
+@pytest.mark.parametrize("G", sorted(SAME_WAVE_LENS))
+def test_too_long_market_shares_a_wave_with_valid_ones(G):
+    """A dozen markets under max_len = G: one wave of the short kernel holds a too-long market (not
+    its first), an empty one and valid ones.  The neighbours (their ``full`` rows too) are
+    bit-exact, the too-long market keeps what ``out`` held, and the fault word reads kFaultTooLong
+    (4)."""
+    lens = SAME_WAVE_LENS[G]
+    bad = int(np.argmax(np.array(lens) > G))
+    per_wave = 64 // G
+    assert 0 < bad < per_wave and 0 in lens[:per_wave] and sum(0 < x <= G for x in lens[:per_wave]) >= 2
+    b = _batch(lens, 10, 20 + G)
+    n = len(b["sid"])
+    long_ = np.zeros(n, bool)
+    long_[b["off"][bad]:b["off"][bad + 1]] = True
+    rest = dict(b, off=_offsets([0 if m == bad else x for m, x in enumerate(lens)]), sid=b["sid"][~long_],
+                prob=b["prob"][~long_])
+    out = _sentinels(n, len(lens))
+    N.check_faults(_dev(), "clean slate")
+    _run(b, max_len=G, out=out)
+    with pytest.raises(N.BCEError, match="device fault 4"):
+        N.check_faults(_dev(), "too long in the wave")
+    got = _host(out)
+    _untouched(got, long_, "same wave")
+    _same({k: got[k][~long_] for k in FIELDS}, _expected(rest), "same wave")
+    full = {k: getattr(out.full, k).cpu().numpy() for k in FIELDS}
+    is_bad = np.arange(len(lens)) == bad
+    _untouched(full, is_bad, "same wave, full")
+    own = orc.consensus_csr(rest["off"], rest["sid"], rest["prob"], b["rel"], b["conf"], b["present"])
+    _same(full, {k: own[k] for k in FIELDS}, "same wave, full", ~is_bad)
+    N.check_faults(_dev(), "fault word is cleared")
+
+
 # ----------------------------------------------------------------------------- walks
 def _walk_fixture(golden_dir, name):
     from bayesian_engine.timeutil import iso_to_us

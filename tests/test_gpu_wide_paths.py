@@ -47,7 +47,10 @@ tables, batches and the oracle's outputs are built once per (max_len, table size
 
 No case provokes a fault word (a market longer than max_len, a sid >= n_sources), and none reaches
 the refill of the market-metadata batch past a workgroup's 64th market (that needs more than
-64 x resident-workgroups markets in one bin)."""
+64 x resident-workgroups markets in one bin).
+
+The last case shares the 2^25 + 1 table: a planned call over it sorts its markets of up to 64
+signals in consensus_long_kernel<true> (csrc/consensus.hip), which no other test reaches."""
 import functools
 
 import numpy as np
@@ -354,3 +357,50 @@ def test_planned_call_merged_bins(mode):
             np.testing.assert_allclose(got, want, rtol=0, atol=TOL, equal_nan=True, err_msg=k)
         else:
             assert np.array_equal(got, want, equal_nan=got.dtype.kind == "f"), k
+
+
+@functools.lru_cache(maxsize=None)
+def _long_lds_batch():
+    from oracle import oracle as orc
+    S = BIG[128]
+    rng = np.random.default_rng(78)
+    lens = np.array([0, 1, 2, 8, 9, 16, 17, 33, 63, 64, 64, 65, 4096, 5, 40], np.int64)
+    rel, conf, present, pool = _table(S)
+    off = np.zeros(len(lens) + 1, np.int64)
+    off[1:] = np.cumsum(lens)
+    n = int(off[-1])
+    sid = pool[(rng.zipf(1.1, n) - 1) % len(pool)].astype(np.int32)  # duplicate runs in every longer market
+    sid[off[9]:off[10]] = rng.choice(pool, 64, replace=False)        # ... and one of 64 distinct sources
+    sid[off[8]], sid[off[8] + 1] = S - 1, 0
+    prob = rng.random(n)
+    prob[off[7] + 3], prob[off[10] - 1] = 1.5, -0.25
+    g = dict(offsets=off, sid=sid, prob=prob)
+    exp = orc.consensus_csr(off, sid, prob, rel, conf, present)
+    _freeze(g, exp)
+    return g, exp
+
+
+def test_planned_call_past_the_seg_key_sorts_short_markets_in_lds():
+    """consensus_long_kernel<true> (csrc/consensus.hip; launch_long_lds): a planned call over
+    2^25 + 1 sources, one more than the 32-bit (sid, index) key of the short-market kernels packs,
+    sorts its markets of up to 64 signals with the u64 bitonic sort in LDS -- the only way to that
+    kernel.  Lengths 0, 1, 2, 8, 9, 16, 17, 33, 63 and 64 (padded sizes 1..64), the top sid and sid
+    0, duplicate runs, out-of-range probabilities; the markets of 65 and of 4096 signals of the same
+    call run in the wide kernel.  EXACT: every output by == with the oracle."""
+    import torch
+    from bayesian_engine import _native as N, batch
+    S = BIG[128]
+    g, exp = _long_lds_batch()
+    assert S > (1 << 25) and (g["sid"] == S - 1).any() and (g["sid"] == 0).any()
+    plan = batch.Plan.build(g["offsets"])
+    assert np.diff(plan.bin_start)[:4].min() > 0  # every bin of n <= 64 has markets
+    T = lambda a: torch.from_numpy(np.array(a)).cuda()  # noqa: E731
+    r = batch.consensus(T(g["offsets"]), T(g["sid"]), T(g["prob"]), _device_table(S), plan=plan)
+    torch.cuda.synchronize()
+    N.check_faults(torch.device("cuda", 0), "long lds")
+    out = {k: getattr(r, k).cpu().numpy() for k in PER_MARKET + PER_UNIQUE}
+    u = exp["n_unique"].astype(np.int64)
+    pos = np.repeat(g["offsets"][:-1], u) + (np.arange(int(u.sum())) - np.repeat(np.cumsum(u) - u, u))
+    for k in PER_MARKET + PER_UNIQUE:
+        got, want = (out[k][pos], exp[k][pos]) if k in PER_UNIQUE else (out[k], exp[k])
+        assert np.array_equal(got, want, equal_nan=got.dtype.kind == "f"), k
