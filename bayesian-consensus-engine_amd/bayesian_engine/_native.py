@@ -114,6 +114,11 @@ _SIGS = {
                                        _vp, _vp]),
     "bce_walk_read_lag": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _f64, _f64,
                                     _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "bce_settle_trace_all": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _f64,
+                                       _f64, _vp, _vp]),
+    "bce_consensus_history_live": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i32,
+                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                             _f64, _f64, _f64, _f64, _vp]),
     "bce_walk_scope_read": (C.c_int, [_i64, _vp, _vp, _vp, _i64, _i32] + [_vp] * 6 + [_i64] + [_vp] * 7 + [_i64] +
                             [_vp] * 6 + [_f64, _f64, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "bce_walk_scope_read_lag": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _i64, _i32] + [_vp] * 6 + [_i64] + [_vp] * 7 +

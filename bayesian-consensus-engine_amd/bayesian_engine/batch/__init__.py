@@ -13,7 +13,7 @@ Layout (include/bce.h):
 Every name lives in one submodule and is re-exported here; a submodule imports only from those
 listed before it: elementwise, tables, consensus, tiebreak, stats, reestimate_csr, settle, pairs,
 walk, glob, score, history, leave_one_out, bootstrap (which imports from score only), update_sweep
-(which imports from walk and score).
+(which imports from walk and score), live (which imports from settle, walk and history).
 """
 from .elementwise import (DECAY_HALF_LIFE_DAYS, DECAY_MINIMUM, DEFAULT_CONFIDENCE, DEFAULT_RELIABILITY, decay_apply,
                           decay_view, outcome_update, pack_flags2, replay_step)
@@ -39,9 +39,10 @@ from .glob import (_GLOB_ANY, _GLOB_CLS, _GLOB_LIT, _GLOB_NEGATE, _GLOB_STAR, GL
 from .score import (SCORE_COUNTS, SCORE_LANES, SCORE_MAX_BINS, SCORE_SEG, SCORE_SUMS, ScorePlan, ScoreResult,
                     _nan_div, _score_segments, score, score_markets, score_sources, walk_sweep,
                     walk_sweep_scoped)
-from .history import (HISTORY_MAX_LEN, HistoryResult, _history_items, _market_of_point, consensus_history, history_at,
-                      score_history, walk_history)
+from .history import (HISTORY_MAX_LEN, HistoryResult, _check_arrival_order, _history_items, _market_of_point,
+                      consensus_history, history_at, score_history, walk_history)
 from .leave_one_out import (LeaveOneOutResult, _loo_items, leave_one_out, score_leave_one_out, walk_leave_one_out)
 from .bootstrap import (BOOT_COUNTS, BOOT_MAX_SETS, BOOT_METRICS, BOOT_TILE, BootstrapResult, boot_units, boot_weights,
                         score_bootstrap)
 from .update_sweep import (UPDATE_MAX_POINTS, commit_update_point, update_steps, walk_sweep_update, walk_trace_grid)
+from .live import LivePlan, _check_live_times, live_trace, walk_history_live

@@ -137,6 +137,24 @@ def consensus_history(offsets: torch.Tensor, sid: torch.Tensor, prob: torch.Tens
                        plan, max_len, offsets_host, check)
 
 
+def _check_arrival_order(offsets: torch.Tensor, arrival_us: torch.Tensor) -> None:
+    """``ValueError`` naming the first signal whose arrival time is earlier than that of the signal
+    before it in the same market (torch only, any device)."""
+    Nsig = arrival_us.numel()
+    if Nsig < 2:
+        return
+    lo0 = offsets[:-1].to(torch.int64)
+    hi0 = offsets[1:].to(torch.int64)
+    down = arrival_us[1:] < arrival_us[:-1]  # down[i]: signal i + 1 is earlier than signal i
+    starts = lo0[(lo0 > 0) & (lo0 < Nsig)]   # a market's first signal has no predecessor
+    down[starts - 1] = False
+    if bool(down.any()):
+        i = int(torch.nonzero(down)[0]) + 1
+        m = int(torch.searchsorted(hi0, torch.tensor(i, device=hi0.device), right=True))
+        raise ValueError(f"arrival times must not decrease inside a market: signal {i} (market {m}) arrived "
+                         f"before signal {i - 1}")
+
+
 def history_at(offsets: torch.Tensor, arrival_us: torch.Tensor, at_us: torch.Tensor,
                check: bool = True) -> torch.Tensor:
     """The point of every market's history that stood at a given time: ``arrival_us`` int64[N] is
@@ -153,15 +171,8 @@ def history_at(offsets: torch.Tensor, arrival_us: torch.Tensor, at_us: torch.Ten
     Nsig = arrival_us.numel()
     lo0 = offsets[:-1].to(torch.int64)
     hi0 = offsets[1:].to(torch.int64)
-    if check and Nsig > 1:
-        down = arrival_us[1:] < arrival_us[:-1]  # down[i]: signal i + 1 is earlier than signal i
-        starts = lo0[(lo0 > 0) & (lo0 < Nsig)]   # a market's first signal has no predecessor
-        down[starts - 1] = False
-        if bool(down.any()):
-            i = int(torch.nonzero(down)[0]) + 1
-            m = int(torch.searchsorted(hi0, torch.tensor(i, device=hi0.device), right=True))
-            raise ValueError(f"arrival times must not decrease inside a market: signal {i} (market {m}) arrived "
-                             f"before signal {i - 1}")
+    if check:
+        _check_arrival_order(offsets, arrival_us)
     if at_us.dim() == 2:
         lo0, hi0 = lo0[:, None], hi0[:, None]
     lo, hi = lo0.expand_as(at_us).clone(), hi0.expand_as(at_us).clone()
@@ -250,7 +261,8 @@ def walk_history(plan, *scopes, offsets: torch.Tensor, prob: torch.Tensor, bins:
     One limit: every market's history uses the reliabilities of ONE read per market -- as they
     stood at that market's own turn (its forecast time for a lagged plan).  They are not re-read
     at every arrival, so an outcome that resolved between two signals of the same market does not
-    move the later points."""
+    move the later points.  :func:`walk_history_live` (batch/live.py) is the history that does
+    re-read them, given every signal's arrival time."""
     wtable = _walk_entry_table(plan, scopes, offsets, prob, trace_kwargs)
     return consensus_history(offsets, plan.pairs.esid, prob.to(torch.float64), wtable, plan=bins, max_len=max_len,
                              offsets_host=offsets_host, out=out, check=check)

@@ -94,20 +94,28 @@ def _walk_times_us(markets, times, resolve_times):
     times = list(times)
     if len(times) != len(markets):
         raise ValueError(f"times has {len(times)} entries for {len(markets)} markets")
-    as_us = lambda t: iso_to_us(t) if isinstance(t, str) else dt_to_us(t)  # noqa: E731
-    t_us = np.array([as_us(t) for t in times], np.int64)
+    t_us = np.array([_as_us(t) for t in times], np.int64)
     if (t_us == NO_TIMESTAMP).any():
         raise ValueError("a market time is empty or unparseable")
-    if resolve_times is None:
-        return t_us, None
+    return t_us, None if resolve_times is None else _resolve_times_us(markets, resolve_times)
+
+
+def _as_us(t) -> int:
+    """An ISO string or a datetime as int64 microseconds (NO_TIMESTAMP: empty or unparseable)."""
+    return iso_to_us(t) if isinstance(t, str) else dt_to_us(t)
+
+
+def _resolve_times_us(markets, resolve_times) -> np.ndarray:
+    """One resolve time per market as int64 microseconds; those of unresolved markets are not
+    looked at (0)."""
     resolve_times = list(resolve_times)
     if len(resolve_times) != len(markets):
         raise ValueError(f"resolve_times has {len(resolve_times)} entries for {len(markets)} markets")
-    r_us = np.array([0 if o is None else (NO_TIMESTAMP if r is None else as_us(r))
+    r_us = np.array([0 if o is None else (NO_TIMESTAMP if r is None else _as_us(r))
                      for (_, o), r in zip(markets, resolve_times)], np.int64)
     if (r_us == NO_TIMESTAMP).any():
         raise ValueError("the resolve time of a resolved market is empty or unparseable")
-    return t_us, r_us
+    return r_us
 
 
 def _check_market_ids(market_ids, M: int) -> None:
@@ -483,16 +491,65 @@ class NamespacedReliabilityStore:
         res = table.walk_forward(plan, b.mtime, offsets=b.off, prob=b.prob, validate=False)
         N.check_faults(b.off.device, "walk_forward")
         results = _walk_dicts(markets, b.offsets, names, res, plan.pairs)
-        touched = sorted(int(x) for x in plan.settle.order.cpu().numpy())
+        return results, self._walked_summary(names, plan.settle, table, namespace, value, target, dry_run)
+
+    def _walked_summary(self, names, splan, table, namespace, value, target, dry_run) -> SettleSummary:
+        """What a committed walk of one scope leaves behind: the final rows of the touched sources
+        of ``splan`` read from ``table``, written back with one ``executemany`` unless ``dry_run``,
+        as the :class:`SettleSummary` of the scope."""
+        touched = sorted(int(x) for x in splan.order.cpu().numpy())
         rel, conf, stamp_us = table.rel.cpu().numpy(), table.conf.cpu().numpy(), table.t_us.cpu().numpy()
-        total, correct = plan.total.cpu().numpy(), plan.correct.cpu().numpy()
+        total, correct = splan.total.cpu().numpy(), splan.correct.cpu().numpy()
         records = {names[i]: NamespacedReliabilityRecord(names[i], namespace, value, float(rel[i]), float(conf[i]),
                                                          us_to_iso(int(stamp_us[i])), False) for i in touched}
         if not dry_run and records:
             self._store._upsert((r.source_id, target, r.reliability, r.confidence, r.updated_at)
                                 for r in records.values())
-        return results, SettleSummary(records, {}, {names[i]: int(total[i]) for i in touched},
-                                      {names[i]: int(correct[i]) for i in touched})
+        return SettleSummary(records, {}, {names[i]: int(total[i]) for i in touched},
+                             {names[i]: int(correct[i]) for i in touched})
+
+    def walk_history_live(self, markets: Sequence[tuple], arrival_times: Sequence[Sequence],
+                          resolve_times: Sequence, domain: Optional[str] = None, dry_run: bool = False):
+        """The consensus history of every market with the reliabilities re-read at every arrival
+        (:func:`batch.walk_history_live`): the reference run online as an event loop -- signal k
+        of market i arrives at ``arrival_times[i][k]`` and ``compute_consensus(signals[:k + 1])``
+        runs with every source fetched by ``get_reliability(sid, scope, apply_decay=True)`` at
+        that time; a market whose outcome is not None runs ``update_reliability`` per signal at
+        ``resolve_times[i]`` and stamps the rows with it.  ``markets`` as in :meth:`walk_forward`
+        (any order); ``arrival_times`` one sequence of ISO strings or datetimes per market, one per
+        signal, not decreasing; ``resolve_times`` one per market (ignored for unresolved markets),
+        no earlier than the market's last arrival.  Returns ``(histories, summary)``: per market
+        one row per signal shaped like ``Market.consensus_history``'s, and the
+        :class:`SettleSummary` of the scope, whose rows are written back unless ``dry_run``."""
+        namespace, value, target = self._update_scope(domain)
+        markets = [(list(signals), outcome) for signals, outcome in markets]
+        arrival_times = [list(a) for a in arrival_times]
+        if len(arrival_times) != len(markets):
+            raise ValueError(f"arrival_times has {len(arrival_times)} entries for {len(markets)} markets")
+        for m, ((signals, _), a) in enumerate(zip(markets, arrival_times)):
+            if len(a) != len(signals):
+                raise ValueError(f"arrival_times[{m}] has {len(a)} entries for {len(signals)} signals")
+        a_us = np.array([_as_us(t) for a in arrival_times for t in a], np.int64)
+        if (a_us == NO_TIMESTAMP).any():
+            raise ValueError("an arrival time is empty or unparseable")
+        r_us = _resolve_times_us(markets, resolve_times)
+        rank = batch.intern(s["sourceId"] for signals, _ in markets for s in signals)
+        if not rank:
+            return [[] for _ in markets], SettleSummary({}, {}, {}, {})
+        names = list(rank)
+        offsets, sid, prob = signals_csr([signals for signals, _ in markets], rank)
+        N.require_gpu()
+        T = batch.to_device(N.device())
+        off, dsid, dprob = T(offsets), T(sid), T(prob)
+        plan = batch.LivePlan.build(off, dsid, dprob, T(_outcome_codes(markets)), len(names), T(a_us), T(r_us))
+        table = self._store.load_table(target, names, device=off.device)
+        h = batch.walk_history_live(plan, table, offsets=off, sid=dsid, prob=dprob, offsets_host=offsets, commit=True)
+        N.check_faults(off.device, "walk_history_live")
+        cons, confd, tot, nu = (x.cpu().numpy() for x in (h.consensus, h.confidence, h.total_weight, h.n_unique))
+        from .market import _history_rows
+        histories = [_history_rows(signals, cons[a:b], confd[a:b], tot[a:b], nu[a:b])
+                     for (signals, _), a, b in zip(markets, offsets[:-1], offsets[1:])]
+        return histories, self._walked_summary(names, plan.settle, table, namespace, value, target, dry_run)
 
     def sweep_decay(self, markets: Sequence[tuple], times: Sequence, half_life_days: Sequence[float],
                     min_rel: Sequence[float], domain: Optional[str] = None, n_bins: int = 10,

@@ -199,6 +199,7 @@ struct PerSignalCall {
   const int32_t* market_list; int64_t n_list;
   const int64_t* bin_start_host; const int64_t* bin_start_dev; int32_t max_len;
   double* consensus; double* confidence; double* total_weight; int32_t* n_unique;
+  bool rows_optional = false;  // relconf may be NULL with n_sources > 0 (the live history: no chain has a bit)
 };
 
 // The body of both entries: the shared argument checks (messages "<op>: ...", the outputs named
@@ -215,7 +216,7 @@ int per_signal_launch(const char* op, const char* outs, const PerSignalCall& c, 
   BCE_REQUIRE(c.n_signals == 0 || (c.sid && c.prob), "%s: sid/prob NULL", op);
   BCE_REQUIRE(c.n_signals == 0 || (c.consensus && c.confidence && c.total_weight && c.n_unique),
               "%s: %s outputs must be non-NULL", op, outs);
-  BCE_REQUIRE(c.n_sources == 0 || c.relconf, "%s: source table is NULL", op);
+  BCE_REQUIRE(c.n_sources == 0 || c.relconf || c.rows_optional, "%s: source table is NULL", op);
   BCE_REQUIRE((uintptr_t)c.relconf % 16 == 0, "%s: relconf must be 16-byte aligned", op);
   BCE_REQUIRE(!(c.bin_start_host && c.bin_start_dev), "%s: one plan, host or device bin boundaries", op);
   const bool planned = c.bin_start_host || c.bin_start_dev;

@@ -606,6 +606,51 @@ int bce_walk_read_lag(int64_t n_entries, const int32_t* usid, const int32_t* ema
                       double default_rel, double default_conf, int mark_cold, int sid_clamped, double* relconf,
                       uint32_t* present_bits, uint8_t* exists, void* stream);
 
+/* ---- live consensus history: the reliabilities re-read at every arrival -----------------------
+ * The event loop above one level finer: the events are (arrival_us[i], m, 0, k) for signal k of
+ * market m and (resolve_time_us[m], m, 1) for every resolved market, ascending.  At an arrival
+ * compute_consensus(signals[:k + 1], table) runs with every source of the prefix fetched by
+ * get_reliability(s, scope, apply_decay=True) with the clock at that arrival; a resolution runs
+ * update_reliability per signal in position order and stamps the resolve time.  Arrivals do not
+ * decrease inside a market and a resolved market resolves no earlier than its last arrival; the
+ * markets may come in any order (the market index only breaks ties).  The chains are compiled in
+ * (resolve time, market, position) order with bit_market[n_bits] the market of every chain bit, as
+ * for bce_walk_lag_queries.
+ *
+ * bce_settle_trace_all: the plan of bce_settle_apply (bits .. chunk_bits; the same workers) and
+ * the start table of bce_settle_trace.  states[2 * g] receives {rel, conf}, raw, after chain bit g
+ * (the global bit index start[s] + k) as one 16-byte store; each exactly once, by the worker that
+ * applied the bit.  The table is only read; the result does not depend on n_long / chunk_bits.
+ * 16 bytes per chain bit.
+ *
+ * bce_consensus_history_live: the arguments, the three launch routes, the outputs and the fault
+ * word of bce_consensus_history, with `states` (16-byte aligned; NULL where n_bits == 0) in the
+ * place of relconf and present_bits not read.  Point i (CSR position) of market j sees bit b of
+ * source s iff (resolve_time_us[bit_market[b]], bit_market[b]) < (arrival_us[i], j)
+ * lexicographically: a prefix of the chain of length pos, found by bisection per (point, source).
+ * pos > 0: the row is states[2 * (start[s] + pos - 1)] stamped with the resolve time of that bit's
+ * market; else the start row rel / conf / t_us of s (present nullable: every row exists), else the
+ * cold defaults, undecayed.  A row that exists is decayed to arrival_us[i] (decay.py:90-145).  A
+ * start that is no range inside [0, n_bits] or a bit_market outside [0, n_markets) raises the fault
+ * word and that read sees no visible bit; nothing is read out of bounds.  A NULL required pointer,
+ * a negative size, n_sources <= 0 with signals, or max_len outside [0, 4096]: BCE_EINVAL before
+ * anything touches the GPU. */
+int bce_settle_trace_all(const uint64_t* bits, int64_t n_bits, const int64_t* start, const int32_t* order,
+                         int64_t n_touched, int64_t n_long, const int64_t* chunk_start, int64_t n_chunks,
+                         int64_t chunk_bits, int32_t n_sources, const double* rel, const double* conf,
+                         const uint8_t* present, double default_rel, double default_conf, double* states,
+                         void* stream);
+int bce_consensus_history_live(const int64_t* offsets, int64_t n_markets, const int32_t* sid, const double* prob,
+                               int64_t n_signals, const double* states, const uint32_t* present_bits,
+                               int32_t n_sources, const int32_t* market_list, int64_t n_list,
+                               const int64_t* bin_start_host, const int64_t* bin_start_dev, int32_t max_len,
+                               double* consensus, double* confidence, double* total_weight, int32_t* n_unique,
+                               const int64_t* arrival_us, const int64_t* start, const int32_t* bit_market,
+                               int64_t n_bits, const int64_t* resolve_time_us, const double* rel,
+                               const double* conf, const int64_t* t_us, const uint8_t* present,
+                               double half_life_days, double min_rel, double default_rel, double default_conf,
+                               void* stream);
+
 /* ---- namespaced walk-forward: the market -> domain -> global fallback at every read ----------
  * The walk above with NamespacedReliabilityStore in the store's place: market m fetches every
  * source with get_reliability(s, market_id, domain_of(m), apply_decay=True)
