@@ -19,6 +19,12 @@ int check_launch(const char* what);
 // Device properties cached per device (CU count for grid sizing).  Thread-safe.
 int cu_count();
 
+// The cap of a persistent grid: per_cu workgroups on every CU, or the debug cap when
+// bce_debug_set_grid_cap has set one (> 0).  Every capped launch sizes its grid through this.
+int64_t grid_cap(int per_cu);
+// The debug cap alone: 0 when none is set.  For a launch whose grid is not sized by the CU count.
+int64_t debug_grid_cap();
+
 // Resident workgroups per CU of `fn` at `threads` threads and `lds` dynamic LDS bytes,
 // cached per (device, kernel, shape); `fallback` when the query fails.  Thread-safe.
 int blocks_per_cu(const void* fn, int threads, size_t lds, int fallback, const char* name = nullptr);

@@ -92,6 +92,10 @@ int cu_count() {
   return c ? c->cus : 256;
 }
 
+static int g_grid_cap = 0;
+int64_t debug_grid_cap() { return g_grid_cap; }
+int64_t grid_cap(int per_cu) { return debug_grid_cap() > 0 ? debug_grid_cap() : (int64_t)cu_count() * per_cu; }
+
 int* split_slot(int ticket, hipStream_t st) {
   DevCtx* c = dev_ctx();
   if (!c || !c->split) return nullptr;
@@ -200,6 +204,11 @@ extern "C" int bce_fault_check(void* stream) {
 
 extern "C" int bce_debug_set_spin_cap(int cap) {
   bce::g_spin_cap = (cap > 0) ? cap : (1 << 22);
+  return BCE_OK;
+}
+
+extern "C" int bce_debug_set_grid_cap(int blocks) {
+  bce::g_grid_cap = (blocks > 0) ? blocks : 0;
   return BCE_OK;
 }
 

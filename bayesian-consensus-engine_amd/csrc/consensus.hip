@@ -515,7 +515,7 @@ int launch_seg_for_len(int max_len, const ConsArgs& a, hipStream_t st) {
 
 int launch_long_lds(const ConsArgs& a, hipStream_t st) {
   if (a.n_list == 0) return BCE_OK;
-  const int64_t cap = (int64_t)cu_count() * 2;
+  const int64_t cap = grid_cap(2);
   const int grid = (int)(a.n_list < cap ? a.n_list : cap);
   hipLaunchKernelGGL((consensus_long_kernel<true>), dim3(grid), dim3(kLongThreads), 0, st, a);
   return check_launch("consensus_long_kernel<lds>");
@@ -525,8 +525,12 @@ int launch_long_global(ConsArgs a, void* scratch, int64_t stride, hipStream_t st
   if (a.n_list == 0) return BCE_OK;
   a.scratch = scratch;
   a.scratch_stride = stride;
-  hipLaunchKernelGGL((consensus_long_kernel<false>), dim3((int)long_scratch_grid(a.n_list)), dim3(kLongThreads), 0,
-                     st, a);
+  // one scratch slice per workgroup of long_scratch_grid, whatever the device: only the debug
+  // cap shrinks this grid, and a smaller grid only leaves slices unused
+  int64_t grid = long_scratch_grid(a.n_list);
+  const int64_t dbg = debug_grid_cap();
+  if (dbg > 0 && grid > dbg) grid = dbg;
+  hipLaunchKernelGGL((consensus_long_kernel<false>), dim3((int)grid), dim3(kLongThreads), 0, st, a);
   return check_launch("consensus_long_kernel<global>");
 }
 

@@ -252,7 +252,7 @@ extern "C" int bce_validate_csr(const int64_t* offsets, int64_t n_markets, const
   if (n_markets == 0) return BCE_OK;
   BCE_REQUIRE(offsets && prob && err_idx, "validate: NULL argument");
   int64_t blocks = (n_markets + 3) / 4;
-  const int64_t cap = (int64_t)cu_count() * 16;
+  const int64_t cap = grid_cap(16);
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(validate_kernel, dim3((int)blocks), dim3(256), 0, as_stream(stream), offsets,
                      n_markets, prob, err_idx);
@@ -285,7 +285,7 @@ extern "C" int bce_table_pack(int64_t n, const double* rel, const double* conf, 
   BCE_REQUIRE(rel && conf && relconf && present_bits, "table_pack: NULL argument");
   BCE_REQUIRE((uintptr_t)relconf % 16 == 0, "table_pack: relconf must be 16-byte aligned");
   int64_t blocks = (n + 255) / 256;
-  const int64_t cap = (int64_t)cu_count() * 16;
+  const int64_t cap = grid_cap(16);
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(table_pack_kernel, dim3((int)blocks), dim3(256), 0, as_stream(stream), n, rel, conf,
                      present, reinterpret_cast<double2*>(relconf), present_bits);

@@ -235,7 +235,7 @@ int launch_persistent(void (*kernel)(KA...), int threads, int fallback, int64_t 
                       hipStream_t st, const A&... args) {
   if (units == 0) return BCE_OK;
   const int per_cu = blocks_per_cu(reinterpret_cast<const void*>(kernel), threads, 0, fallback, name);
-  const int64_t cap = (int64_t)cu_count() * per_cu;
+  const int64_t cap = grid_cap(per_cu);
   const int grid = (int)(units < cap ? units : cap);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, st, args...);
   return check_launch(name);

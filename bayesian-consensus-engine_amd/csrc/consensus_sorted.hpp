@@ -185,7 +185,7 @@ int launch_market_block(void (*fn)(KA...), int elem_bytes, int64_t max_len, int6
   const int rc = ensure_dynamic_lds(f, elem_bytes * kLongMaxLds);
   if (rc) return rc;
   const int per_cu = blocks_per_cu(f, threads, lds, 1, name);
-  const int64_t cap = (int64_t)cu_count() * per_cu;
+  const int64_t cap = grid_cap(per_cu);
   const int grid = (int)(n_list < cap ? n_list : cap);
   hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, st, args..., (int)P);
   return check_launch(name);

@@ -560,7 +560,7 @@ int launch_tab32_t(ConsArgs a, hipStream_t st) {
   const int per_cu = blocks_per_cu(fn, 64 * kTabWaves, lds, 1, HYB ? "consensus_tab32_kernel<hybrid>"
                                                                   : "consensus_tab32_kernel");
   const int64_t blocks = (tiles + kTabWaves - 1) / kTabWaves;
-  const int64_t cap = (int64_t)cu_count() * per_cu;
+  const int64_t cap = grid_cap(per_cu);
   const int grid = (int)(blocks < cap ? blocks : cap);
   hipLaunchKernelGGL((consensus_tab32_kernel<HYB>), dim3(grid), dim3(64 * kTabWaves), lds, st, a);
   return check_launch("consensus_tab32_kernel");

@@ -807,7 +807,7 @@ WideKernel wide_kernel_for(int64_t max_len, int32_t mode, int32_t n_sources) {
 }
 
 int64_t resident(const WideKernel& k) {
-  return (int64_t)cu_count() * blocks_per_cu(reinterpret_cast<const void*>(k.fn), k.threads, 0, 1, "consensus_wide_kernel");
+  return grid_cap(blocks_per_cu(reinterpret_cast<const void*>(k.fn), k.threads, 0, 1, "consensus_wide_kernel"));
 }
 
 }  // namespace

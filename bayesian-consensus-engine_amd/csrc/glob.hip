@@ -215,7 +215,7 @@ extern "C" int bce_glob_match(const uint8_t* name_bytes, int64_t n_bytes, const 
   BCE_REQUIRE(name_tiles <= (int64_t)INT32_MAX, "glob_match: more than 2^31 - 1 name tiles");
   // pattern stripes: enough workgroups to fill the device, as few restagings of the names as that allows
   const int64_t n_tiles = (P + kGlobPT - 1) / kGlobPT;
-  int64_t stripes = ((int64_t)cu_count() * 16 + name_tiles - 1) / name_tiles;
+  int64_t stripes = (grid_cap(16) + name_tiles - 1) / name_tiles;
   if (stripes > n_tiles) stripes = n_tiles;
   if (stripes > 65535) stripes = 65535;
   if (stripes < 1) stripes = 1;

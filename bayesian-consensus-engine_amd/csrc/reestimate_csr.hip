@@ -224,7 +224,7 @@ extern "C" int bce_reestimate_csr_agreement(int64_t n_entries, const int32_t* us
   if (n_entries == 0) return BCE_OK;
   BCE_REQUIRE(usid && votes && emarket && outcome && correct && total, "reestimate_csr_agreement: NULL argument");
   int64_t blocks = (n_entries + 255) / 256;
-  const int64_t cap = (int64_t)cu_count() * 8;
+  const int64_t cap = grid_cap(8);
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(reestimate_csr_agreement_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream),
                      n_entries, usid, votes, emarket, outcome, n_markets, n_sources,

@@ -510,7 +510,7 @@ extern "C" int bce_agreement_stats(const int64_t* offsets, int64_t n_markets, co
   if (n_markets == 0) return BCE_OK;
   BCE_REQUIRE(offsets && sid && prob && outcome && correct && total, "agreement: NULL argument");
   int64_t blocks = (n_markets + 3) / 4;
-  const int64_t cap = (int64_t)cu_count() * 16;
+  const int64_t cap = grid_cap(16);
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(agreement_kernel, dim3((int)blocks), dim3(256), 0, as_stream(stream), offsets,
                      n_markets, sid, prob, outcome, correct, total);
@@ -582,7 +582,7 @@ extern "C" int bce_reestimate_agreement_votes(const uint64_t* vote_bits, int64_t
   const int64_t K = (M + 63) / 64;
   const int64_t ab = (A + 255) / 256;
   // enough blocks to fill the chip: slices of the vote words across blockIdx.y
-  int64_t ks = (4 * (int64_t)cu_count() * 8 + ab - 1) / ab;
+  int64_t ks = (grid_cap(32) + ab - 1) / ab;
   if (ks > K) ks = K;
   if (ks > 65535) ks = 65535;
   if (ks < 1) ks = 1;
@@ -620,7 +620,7 @@ extern "C" int bce_reestimate_consensus_votes_mfma(const double* P, int64_t A, i
                      nflag, flags);
   rc = check_launch("reestimate_votes_mfma_kernel");
   if (rc) return rc;
-  hipLaunchKernelGGL(reestimate_fixup_kernel, dim3((unsigned)cu_count() * 4), dim3(256), 0, st, P, A, ld, w, nflag,
+  hipLaunchKernelGGL(reestimate_fixup_kernel, dim3((unsigned)grid_cap(4)), dim3(256), 0, st, P, A, ld, w, nflag,
                      flags, consensus, reinterpret_cast<unsigned long long*>(cvote_words));
   rc = check_launch("reestimate_fixup_kernel");
   if (rc) return rc;

@@ -325,7 +325,7 @@ template <bool EXOTIC>
 static int launch_tb_short(const TbArgs& a, const int32_t* market_list, int64_t nl, int32_t max_len, void* stream) {
   if (max_len <= kTbLpmMax) return launch_tb_lpm<EXOTIC>(a, market_list, nl, max_len, stream);
   int64_t blocks = (nl + 3) / 4;
-  const int64_t cap = (int64_t)cu_count() * 16;
+  const int64_t cap = grid_cap(16);
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(tiebreak_wave_kernel<EXOTIC>, dim3((int)blocks), dim3(256), 0, as_stream(stream), a,
                      market_list, nl);
@@ -358,7 +358,7 @@ static int launch_tb_long(const TbArgs& a, const int32_t* list, int64_t n_list, 
   hipStream_t st = as_stream(stream);
   if (max_len <= kTbMax) {
     int64_t blocks = n_list;
-    const int64_t cap = (int64_t)cu_count() * 2;
+    const int64_t cap = grid_cap(2);
     if (blocks > cap) blocks = cap;
     hipLaunchKernelGGL((tiebreak_block_kernel<true, EXOTIC>), dim3((int)blocks), dim3(kTbThreads), 0, st, a, list,
                        n_list, nullptr, (int64_t)0);
@@ -371,7 +371,7 @@ static int launch_tb_long(const TbArgs& a, const int32_t* list, int64_t n_list, 
   // longest market; the grid shrinks instead of the scratch growing past 1 GiB (one
   // 10M-agent market beside other long ones would otherwise ask for CUs x 256 MB)
   int64_t blocks = n_list;
-  int64_t cap = (int64_t)cu_count();
+  int64_t cap = grid_cap(1);
   const int64_t by_budget = ((int64_t)1 << 30) / (16 * P);
   if (cap > by_budget) cap = by_budget > 0 ? by_budget : 1;
   if (blocks > cap) blocks = cap;

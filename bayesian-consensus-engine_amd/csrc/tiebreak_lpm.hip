@@ -957,7 +957,7 @@ int launch_tb_lpm(const TbArgs& a, const int32_t* market_list, int64_t nl, int32
                       (!a.g_avgconf || al16(a.g_avgconf)) && (!a.g_maxrel || al16(a.g_maxrel));
   TbLpmFn fn = tb_lpm_pick<EXOTIC>(listed, gather, np, split);
   const int per_cu = blocks_per_cu(reinterpret_cast<const void*>(fn), 64 * kTbLpmWaves, 0, 1, "tiebreak_lpm_kernel");
-  const int64_t cap = (int64_t)cu_count() * per_cu;
+  const int64_t cap = grid_cap(per_cu);
   if (blocks > cap) blocks = cap;
   if (split && blocks * kTbLpmWaves > kSplitWords) {  // one split word per wave of the grid
     split = false;

@@ -45,9 +45,7 @@ the top sid and two sids that agree in their low 32 - IB bits (0 and 2^(32 - IB)
 Large tables are np.full of the cold default row with only a fixed pool of rows overwritten;
 tables, batches and the oracle's outputs are built once per (max_len, table size) and frozen.
 
-No case provokes a fault word (a market longer than max_len, a sid >= n_sources), and none reaches
-the refill of the market-metadata batch past a workgroup's 64th market (that needs more than
-64 x resident-workgroups markets in one bin).
+No case provokes a fault word (a market longer than max_len, a sid >= n_sources).
 
 The last case shares the 2^25 + 1 table: a planned call over it sorts its markets of up to 64
 signals in consensus_long_kernel<true> (csrc/consensus.hip), which no other test reaches."""
